@@ -6,6 +6,10 @@ image_size=224 patch_size=14 iters=12, bf16, synthetic 224x224 images,
 random-init weights. Weak scaling: fixed per-GPU batch (default 64).
 
 Single GPU:   python bench.py --gpus 1 --steps K --warmup W
+              (a plain run only sets up, warms up, times K steps and prints
+              the result line; --dump-outputs DIR also saves what the last
+              timed step computed; --full is where any measurement beyond
+              the headline figure belongs)
 Multi GPU:    python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
                   --master-addr 127.0.0.1 bench.py --gpus N --steps K --warmup W
 """
@@ -16,8 +20,16 @@ import os
 import sys
 import time
 
+import numpy as np
 import torch
 import torch.distributed as dist
+
+# --dump-outputs budget: tensors larger than this many elements are saved as
+# a fixed, seeded sample (1 Mi elements * 4 B = 4 MiB per array; the model
+# has four such tensors, each dumped as bf16 parameter and fp32 master copy,
+# so a dump stays well inside the 64 MB total)
+DUMP_MAX_ELEMS = 1 << 20
+DUMP_MAX_BYTES = 64 * 10 ** 6
 
 
 def parse_args():
@@ -48,7 +60,37 @@ def parse_args():
     p.add_argument("--profile", action="store_true",
                    help="emit roctx ranges around each timed step (pair "
                         "with rocprofv3 --marker-trace)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed "
+                        "step computed to DIR/<name>.npy (float32; large "
+                        "tensors as a fixed seeded sample): train = loss + "
+                        "updated parameters (and their fp32 master copies), "
+                        "infer = final levels")
+    p.add_argument("--full", action="store_true",
+                   help="also run every measurement beyond the headline "
+                        "figure; this benchmark has none (comparison arms "
+                        "are separate --impl/--mode runs), so the flag "
+                        "currently adds nothing")
     return p.parse_args()
+
+
+def dump_outputs(out_dir, named):
+    """Write each (name, tensor) as out_dir/<name>.npy in float32. Tensors
+    above the per-tensor cap are sampled at fixed positions (seeded
+    generator, the same positions every run and every build). The cap is
+    DUMP_MAX_ELEMS, or, for configurations with so many mid-size tensors
+    that this would exceed DUMP_MAX_BYTES, an equal share of the budget."""
+    os.makedirs(out_dir, exist_ok=True)
+    cap = DUMP_MAX_ELEMS
+    if 4 * sum(min(t.numel(), cap) for _, t in named) > DUMP_MAX_BYTES:
+        cap = DUMP_MAX_BYTES // 4 // len(named)
+    gen = torch.Generator().manual_seed(0)
+    for name, t in named:
+        t = t.detach()
+        if t.numel() > cap:
+            idx = torch.randint(t.numel(), (cap,), generator=gen)
+            t = t.reshape(-1)[idx.to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.float().cpu().numpy())
 
 
 def main():
@@ -87,10 +129,11 @@ def main():
         if args.impl == "native":
             model.enable_graphs()
         loss = 0.0
+        last_out = [None]
 
         def step(x, iters):
             with torch.no_grad():
-                model(x, iters=iters)
+                last_out[0] = model(x, iters=iters)
             return 0.0
     else:
         trainer = DenoisingTrainer(model, distributed=distributed,
@@ -125,6 +168,23 @@ def main():
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = t.item()
+
+    if args.dump_outputs and rank == 0:
+        if args.mode == "infer":
+            named = [("levels", last_out[0])]
+        else:
+            named = [("loss", torch.as_tensor(loss))]
+            named += [("model." + n, q)
+                      for n, q in model.named_parameters()]
+            named += [("decoder." + n, q)
+                      for n, q in trainer.decoder.named_parameters()]
+            if trainer.master is not None:
+                # fp32 master copies (trainer._params order): what the
+                # optimizer really computed, before rounding to bf16
+                names = [n for n, _ in named[1:]]
+                named += [("master." + n, mw)
+                          for n, mw in zip(names, trainer.master)]
+        dump_outputs(args.dump_outputs, named)
 
     if rank == 0:
         n_gpus = world if distributed else 1

@@ -7,6 +7,7 @@ leaves to the user. Launch one process per GPU via torchrun for DP:
 """
 import os
 import sys
+import tempfile
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -37,5 +38,6 @@ for step in range(steps):
     if step % 5 == 0:
         print(f"step {step}: loss {loss:.4f}")
 
-trainer.save_checkpoint("/tmp/glom_example_ckpt.pt")
+with tempfile.TemporaryDirectory() as ckpt_dir:
+    trainer.save_checkpoint(os.path.join(ckpt_dir, "glom_example_ckpt.pt"))
 print("checkpoint saved; state_dict interchanges with the reference package")

@@ -352,9 +352,10 @@ std::vector<torch::Tensor> grouped_ff_bwd(
         p.epilogue = EPI_GELUGRAD;
         p.aux_base = Hpre.data_ptr(); p.aux_sin = M * m4; p.aux_ld = m4;
         if (dh_nt3) {
-            db1f = torch::zeros({G, m4}, opts.dtype(at::kFloat));
+            // per-64-row partials, fully written by the epilogue
+            db1f = torch::empty({G, M / 64, m4}, opts.dtype(at::kFloat));
             p.colsum_out = db1f.data_ptr<float>();
-            p.colsum_sin = m4;
+            p.colsum_sin = (M / 64) * m4;
         }
         run_gemm(p, s, opts, true);
     }
@@ -411,7 +412,10 @@ std::vector<torch::Tensor> grouped_ff_bwd(
     }
     torch::Tensor dB1;
     if (dh_nt3) {
-        dB1 = db1f.flatten().to(at::kBFloat16);
+        dB1 = torch::empty({G * m4}, opts);
+        launch_colsum_fin(db1f.data_ptr<float>(), dB1.data_ptr(), (int)G,
+                          m4, (int)(M / 64), s);
+        check_launch();
     } else {
         // native deterministic column sum (replaces ATen .sum(1))
         dB1 = torch::empty({G * m4}, opts);
@@ -810,14 +814,18 @@ std::vector<torch::Tensor> ff_bwd_dh(torch::Tensor dY, torch::Tensor w2t,
     p.epilogue = EPI_GELUGRAD;
     p.aux_base = Hpre.data_ptr(); p.aux_sin = M * m4; p.aux_ld = m4;
     if (fused) {
-        db1f = torch::zeros({G, m4}, opts.dtype(at::kFloat));
+        // per-64-row partials, fully written by the epilogue
+        db1f = torch::empty({G, M / 64, m4}, opts.dtype(at::kFloat));
         p.colsum_out = db1f.data_ptr<float>();
-        p.colsum_sin = m4;
+        p.colsum_sin = (M / 64) * m4;
     }
     run_gemm(p, s, opts, true);
     torch::Tensor dB1;
     if (fused) {
-        dB1 = db1f.flatten().to(at::kBFloat16);
+        dB1 = torch::empty({G * m4}, opts);
+        launch_colsum_fin(db1f.data_ptr<float>(), dB1.data_ptr(), (int)G,
+                          m4, (int)(M / 64), s);
+        check_launch();
     } else {
         dB1 = torch::empty({G * m4}, opts);
         auto cws = torch::empty({(long)G * colsum_rb(M) * m4},
@@ -1040,6 +1048,21 @@ torch::Tensor dpos(torch::Tensor dLevels) {
     return out;
 }
 
+// (M, C) bf16 -> (C,) bf16 column sum, f32 accumulation in fixed order
+// (bias gradient of a plain Linear, e.g. the trainer's decoder)
+torch::Tensor colsum(torch::Tensor x) {
+    CHECK_IN(x);
+    TORCH_CHECK(x.dim() == 2, "colsum expects (M, C)");
+    const int64_t M = x.size(0), C = x.size(1);
+    auto out = torch::empty({C}, x.options());
+    auto ws = torch::empty({(long)colsum_rb(M) * C},
+                           x.options().dtype(at::kFloat));
+    launch_colsum(x.data_ptr(), ws.data_ptr<float>(), out.data_ptr(), 1, M,
+                  C, cur_stream());
+    check_launch();
+    return out;
+}
+
 // ------------------------------------------------------------------ //
 // fused AdamW: one kernel pass over all parameter tensors (bf16 grads ->
 // fp32 m/v/master -> bf16 param write-back) with the deterministic
@@ -1135,6 +1158,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "patchify + embed GEMM (K1)");
     m.def("patch_embed_bwd", &patch_embed_bwd, "patch embed backward");
     m.def("dpos", &dpos, "positional embedding gradient reduction");
+    m.def("colsum", &colsum, "fixed-order column sum (M,C) -> (C,)");
     m.def("fused_adamw", &fused_adamw,
           "fused AdamW + global-norm grad clip (torch semantics)");
     m.def("add4_into", &add4_into, "fused 4-way elementwise sum");

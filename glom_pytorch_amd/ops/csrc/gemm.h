@@ -45,8 +45,12 @@ struct GemmParams {
     const void* pos; long pos_ld;
 
     // optional fused column sum of C over the row axis (bias gradient):
-    // nt_fast3 adds its tile's column sums into colsum_out[p][col] (f32,
-    // caller-zeroed) during the epilogue, saving a full re-read of C.
+    // the 256-wide NT kernels store per-row-span partial column sums into
+    // colsum_out[p][M/64][N] (f32, no atomics: every (64-row slot, column)
+    // has exactly one writer; a writer spanning several slots zeroes the
+    // rest) during the epilogue, saving a full re-read of C. The caller
+    // reduces the slots in fixed order (launch_colsum_fin), so the result
+    // is run-to-run bitwise reproducible. colsum_sin = (M/64)*N.
     float* colsum_out; long colsum_sin;
 
     // attention-fusion extras (EPI_SOFTMAX / EPI_SMBWD)

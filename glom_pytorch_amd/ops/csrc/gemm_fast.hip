@@ -35,6 +35,24 @@ __device__ __forceinline__ int swz_row(int row) {
     return (row ^ (row >> 3)) & 7;
 }
 
+// Fused colsum partial (GemmParams::colsum_out, layout [M/64][N]): the one
+// writer of rows [row0, row0 + 64*nslots) x column `col` stores its sum in
+// the span's first slot and zeroes the others. Plain stores, no atomics.
+__device__ __forceinline__ void colsum_store(
+        float* colp, long N, long row0, int nslots, long col, float v) {
+    float* q = colp + (row0 >> 6) * N + col;
+    q[0] = v;
+    for (int k = 1; k < nslots; k++) q[(long)k * N] = 0.f;
+}
+
+// Sum of `v` over the 4 lanes {l, l^16, l^32, l^48} (the kq groups of the
+// MFMA C layout), identical bits in all four.
+__device__ __forceinline__ float kq_sum(float v) {
+    v += __shfl_xor(v, 16);
+    v += __shfl_xor(v, 32);
+    return v;
+}
+
 // Issue this wave's share of one operand tile (128 rows x 64 cols bf16 =
 // 16 KB = 16 DMA chunks of 1 KB; 4 chunks per wave) into a LINEAR LDS
 // image, pre-swizzling the source address so a swizzled ds_read_b128 is
@@ -706,14 +724,14 @@ __global__ __launch_bounds__(NT3) void gemm_nt_fast3_kernel(GemmParams p) {
     }
     if (p.colsum_out) {
         // fused bias-grad: this tile's column sums (C values still live in
-        // the LDS staging image) accumulated into the f32 output
+        // the LDS staging image) stored as this row tile's f32 partial
         float* outp = p.colsum_out + (long)(pid % p.nInner) * p.colsum_sin;
         int c = threadIdx.x;
         if (c < BN3) {
             float ssum = 0.f;
             for (int r = 0; r < 128; r++)
                 ssum += bf2f(smem[r * EPI2_ROW + c]);
-            atomicAdd(&outp[n0 + c], ssum);
+            colsum_store(outp, p.N, m0, BM / 64, n0 + c, ssum);
         }
     }
 }
@@ -1175,14 +1193,14 @@ __global__ __launch_bounds__(NT3) void gemm_nt_fast4_kernel(GemmParams p) {
     }
     if (p.colsum_out) {
         // fused bias-grad: this tile's column sums (C values still live in
-        // the LDS staging image) accumulated into the f32 output
+        // the LDS staging image) stored as this row tile's f32 partial
         float* outp = p.colsum_out + (long)(pid % p.nInner) * p.colsum_sin;
         int c = threadIdx.x;
         if (c < BN3) {
             float ssum = 0.f;
             for (int r = 0; r < 128; r++)
                 ssum += bf2f(smem[r * EPI2_ROW + c]);
-            atomicAdd(&outp[n0 + c], ssum);
+            colsum_store(outp, p.N, m0, BM / 64, n0 + c, ssum);
         }
     }
 }
@@ -1202,7 +1220,7 @@ void launch_gemm_nt_fast4(const GemmParams& p, hipStream_t stream) {
 // K-amortization) — is paid once per PERSIST tiles. The epilogue runs from
 // registers (scalar stores; no LDS image — the ring owns the arena) in the
 // shadow of the next tile's MFMAs. Supports alpha/bias/colscale/GELUGRAD
-// and the fused f32 colsum (per-wave atomics, 2/column/tile); no
+// and the fused f32 colsum (one partial store per wave half/column/tile); no
 // softmax/pair/table-C epilogues — the dispatcher routes those to nt4.
 template <int PERSIST>
 __global__ __launch_bounds__(NT3) void gemm_nt_fast5p_kernel(GemmParams p) {
@@ -1390,8 +1408,7 @@ __global__ __launch_bounds__(NT3) void gemm_nt_fast5p_kernel(GemmParams p) {
                         ushort_t cb = f2bf(vv[j16] + bvv[j16]);
                         // colsum over the bf16-ROUNDED stored values,
                         // matching the LDS-epilogue colsum bit for bit
-                        // per summand (only the add order differs, and
-                        // that was already atomic-nondeterministic)
+                        // per summand (only the fixed add order differs)
                         colacc[j16] += bf2f(cb);
                         cbv[j16] = cb;
                         crow[j16 * 16] = cb;
@@ -1415,9 +1432,14 @@ __global__ __launch_bounds__(NT3) void gemm_nt_fast5p_kernel(GemmParams p) {
                 }
             }
             if (colp) {
+                // this wave's 64 rows: fold the 4 kq lane groups, one store
 #pragma unroll
-                for (int j16 = 0; j16 < 4; j16++)
-                    atomicAdd(&colp[n0 + wn + j16 * 16 + lrow], colacc[j16]);
+                for (int j16 = 0; j16 < 4; j16++) {
+                    float cs = kq_sum(colacc[j16]);
+                    if (kq == 0)
+                        colsum_store(colp, p.N, mt0 + wm, 1,
+                                     n0 + wn + j16 * 16 + lrow, cs);
+                }
             }
             if (g + 2 < TOT) stage_g((g + 2) % 3, g + 2);
         }
@@ -1681,9 +1703,14 @@ __global__ __launch_bounds__(NT8) void gemm_nt_fast8p_kernel(GemmParams p) {
         }
     }
     if (colp) {
+        // this wave's 128 rows: fold the 4 kq lane groups, one store
 #pragma unroll
-        for (int j16 = 0; j16 < 4; j16++)
-            atomicAdd(&colp[n0 + wn + j16 * 16 + lrow], colacc[j16]);
+        for (int j16 = 0; j16 < 4; j16++) {
+            float cs = kq_sum(colacc[j16]);
+            if (kq == 0)
+                colsum_store(colp, p.N, (long)m0 + wm, 2,
+                             n0 + wn + j16 * 16 + lrow, cs);
+        }
     }
 }
 

@@ -18,6 +18,10 @@ void launch_slice_cols(const void* src, void* dst, long rows, int Kp,
 int colsum_rb(long M);
 void launch_colsum(const void* in, float* partials, void* out, int nprob,
                    long M, long C, hipStream_t s);
+// second stage alone: partials (P, RB, C) f32 -> out (P, C) bf16, summed in
+// fixed order (for partials written by a GEMM's fused-colsum epilogue).
+void launch_colsum_fin(const float* partials, void* out, int nprob, long C,
+                       int RB, hipStream_t s);
 // dLevels (B,N,L,d) -> dPos (N,d) = sum over b and l in [1,L).
 // partials: caller-provided (BCH, N, d) f32 workspace (BCH batch chunks);
 // pass nullptr/0 for the scalar single-stage fallback.

@@ -187,6 +187,14 @@ void launch_colsum(const void* in, float* partials, void* out, int nprob,
                        dim3(NT256), 0, s, partials, (ushort_t*)out, C, RB);
 }
 
+// stage 2 alone, for partials a GEMM epilogue already wrote
+// (GemmParams::colsum_out): out[p][c] = bf16(sum_rb partials[p][rb][c])
+void launch_colsum_fin(const float* partials, void* out, int nprob, long C,
+                       int RB, hipStream_t s) {
+    hipLaunchKernelGGL(k_colsum_fin, dim3(cdivl(C, NT256), nprob),
+                       dim3(NT256), 0, s, partials, (ushort_t*)out, C, RB);
+}
+
 // --------------------------------------------------------------------- //
 // positional-embedding gradient: dPos[n, q] = sum_b sum_{l=1..L-1}
 // dLevels[b, n, l, q]  (deterministic: fixed b-then-l order per thread)

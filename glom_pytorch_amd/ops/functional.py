@@ -44,6 +44,31 @@ class PatchEmbedFn(torch.autograd.Function):
         return (dImg if need_dimg else None), dW, dB, None
 
 
+class LinearFixedBiasGradFn(torch.autograd.Function):
+    """nn.Linear on bf16 GPU tensors with the stock forward and data/weight
+    gradients, but the bias gradient from the native two-launch fixed-order
+    column sum. Inside overlapped training steps the stock single-launch
+    reduction occasionally returned a different block of columns for a
+    bitwise identical input (cause not established, see
+    docs/ARCHITECTURE.md "Numerics contract"); this one repeats bitwise."""
+
+    @staticmethod
+    def forward(ctx, x, w, b):
+        ctx.save_for_backward(x, w)
+        return torch.nn.functional.linear(x, w, b)
+
+    @staticmethod
+    def backward(ctx, g):
+        ext = _load_extension()
+        x, w = ctx.saved_tensors
+        g2 = g.reshape(-1, g.shape[-1]).contiguous()
+        x2 = x.reshape(-1, x.shape[-1])
+        dx = g2.mm(w).view_as(x) if ctx.needs_input_grad[0] else None
+        dw = g2.t().mm(x2) if ctx.needs_input_grad[1] else None
+        db = ext.colsum(g2) if ctx.needs_input_grad[2] else None
+        return dx, dw, db
+
+
 class TrajectoryFn(torch.autograd.Function):
     """return_all trajectory (reference glom_pytorch.py:126,145-148)
     without the torch.stack copy: every step already wrote its output into

@@ -23,13 +23,26 @@ from glom_pytorch_amd.parallel.ddp import BucketedDDP
 from glom_pytorch_amd.parallel.failure import Heartbeat
 
 
+class _DecoderLinear(nn.Linear):
+    """nn.Linear whose bf16 GPU bias gradient comes from the native
+    fixed-order column sum (run-to-run reproducible); everything else, and
+    every other device/dtype, is the stock layer."""
+
+    def forward(self, x):
+        if (x.is_cuda and x.dtype == torch.bfloat16
+                and self.bias is not None and torch.is_grad_enabled()):
+            from glom_pytorch_amd.ops.functional import LinearFixedBiasGradFn
+            return LinearFixedBiasGradFn.apply(x, self.weight, self.bias)
+        return super().forward(x)
+
+
 class DenoisingDecoder(nn.Sequential):
     """Top-level embedding -> image patches (README.md:78-81)."""
 
     def __init__(self, dim: int, image_size: int, patch_size: int):
         side = image_size // patch_size
         super().__init__(
-            nn.Linear(dim, patch_size ** 2 * 3),
+            _DecoderLinear(dim, patch_size ** 2 * 3),
             Rearrange("b (h w) (p1 p2 c) -> b c (h p1) (w p2)",
                       h=side, w=side, p1=patch_size, p2=patch_size),
         )

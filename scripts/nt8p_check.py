@@ -47,7 +47,7 @@ def ffpair(B, N, L, d, mode):
             continue
         relerr = ((a.float()-b.float()).norm() /
                   a.float().norm().clamp_min(1e-9)).item()
-        tol = 2e-2 if nm == "dB1" else 1e-2   # atomic colsum order
+        tol = 2e-2 if nm == "dB1" else 1e-2   # colsum add order differs by kernel
         print(f"  mode{mode} {nm}: bitwise={torch.equal(a,b)} relerr={relerr:.2e}")
         assert relerr < tol, (nm, relerr)
 

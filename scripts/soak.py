@@ -38,7 +38,7 @@ print(json.dumps({"first10": first, "last10": last, "min": min(losses),
 # Criterion: the loss fell materially, stayed finite, and stays bounded.
 # The UNNORMALIZED reference math makes the trajectory chaotic: a
 # one-summand rounding change in a single bias grad (dB1 colsum ordering,
-# which is atomic-nondeterministic anyway) measurably shifts where the
+# which differs between the kernels that fuse it) measurably shifts where the
 # loss wanders after a few hundred steps, so an exact last<=first check
 # is not meaningful — boundedness is.
 assert all(l == l for l in losses), "non-finite loss"

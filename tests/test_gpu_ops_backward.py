@@ -118,3 +118,67 @@ def test_full_graph_token_grad_nonzero():
     for n, p in m.named_parameters():
         assert p.grad is not None, n
         assert p.grad.float().norm().item() > 0, n
+
+
+@pytest.mark.parametrize("rows,cin,cout", [
+    ((3, 50), 64, 588),     # cout % 8 != 0: scalar colsum path, 3-D input
+    ((16384,), 64, 128),    # more rows than one colsum chunk set, 8-wide path
+])
+def test_linear_fixed_bias_grad(rows, cin, cout):
+    """LinearFixedBiasGradFn: forward is the stock bf16 result bit for bit;
+    dx/dw are f32-accumulated GEMMs rounded once to bf16 (relative norm
+    error below one bf16 ulp, 2^-8, against fp32 math); db is the
+    f32-accumulated column sum of the bf16 grad rounded once to bf16, so
+    each element is within one bf16 ulp of the fp32 sum, and it repeats
+    bitwise."""
+    from glom_pytorch_amd.ops.functional import LinearFixedBiasGradFn
+    torch.manual_seed(11)
+    bf = torch.bfloat16
+    x = torch.randn(*rows, cin, device=DEV, dtype=bf, requires_grad=True)
+    w = (torch.randn(cout, cin, device=DEV, dtype=bf) * 0.1).requires_grad_()
+    b = torch.randn(cout, device=DEV, dtype=bf, requires_grad=True)
+    g = torch.randn(*rows, cout, device=DEV, dtype=bf)
+
+    y = LinearFixedBiasGradFn.apply(x, w, b)
+    dx, dw, db = torch.autograd.grad(y, (x, w, b), g)
+    assert torch.equal(y, F.linear(x, w, b))
+    g2, x2 = g.float().reshape(-1, cout), x.detach().float().reshape(-1, cin)
+    assert _rel(dx, (g2 @ w.detach().float()).view_as(x)) < 2.0 ** -8
+    assert _rel(dw, g2.t() @ x2) < 2.0 ** -8
+    db_ref = g2.sum(0)
+    # one bf16 ulp of rounding plus f32 summation-order slack
+    tol = db_ref.abs() * 2.0 ** -8 + 1e-3
+    assert ((db.float() - db_ref).abs() <= tol).all()
+    db2 = torch.autograd.grad(LinearFixedBiasGradFn.apply(x, w, b), b, g)[0]
+    assert torch.equal(db, db2)
+
+
+@pytest.mark.parametrize("B,d,kernel", [
+    (2, 64, "nt4"),      # M=512: persistent grid 4*1*2 = 8 < 96 -> nt4
+    (24, 64, "nt5p"),    # M=6144: M % 512 == 0, grid 4*12*2 = 96 -> nt5p
+    (32, 2048, "nt8p"),  # M=8192, K=2048: grid 4*32*2 = 256 -> nt8p
+])
+def test_fused_db1_colsum_fixed_order(B, d, kernel):
+    """dB1 fused into the dH GEMM epilogue (per-64-row partial stores +
+    k_colsum_fin), on one shape per kernel that carries the fusion. It must
+    repeat bitwise, and match the standalone two-stage colsum of the stored
+    bf16 dHpre: both are f32 sums of the same bf16 values rounded once to
+    bf16, so they differ by at most one bf16 ulp (2^-7 relative) plus the
+    f32 reordering bound M * 2^-24 * sum|x|."""
+    from glom_pytorch_amd.ops import _load_extension
+    ext = _load_extension()
+    torch.manual_seed(3)
+    bf = torch.bfloat16
+    G, N, m4 = 2, 256, 1024
+    M = B * N
+    dY = torch.randn(B, N, G, d, device=DEV, dtype=bf)
+    w2t = torch.randn(G, m4, d, device=DEV, dtype=bf) * 0.05
+    Hpre = torch.randn(G, M, m4, device=DEV, dtype=bf)
+    dH, dB1 = ext.ff_bwd_dh(dY, w2t, Hpre)
+    dH2, dB1b = ext.ff_bwd_dh(dY, w2t, Hpre)
+    assert torch.equal(dH, dH2)
+    assert torch.equal(dB1, dB1b)
+    ref = torch.stack([ext.colsum(dH[g]) for g in range(G)]).flatten().float()
+    abssum = dH.float().abs().sum(1).flatten()
+    tol = ref.abs() * 2.0 ** -7 + M * 2.0 ** -24 * abssum
+    assert ((dB1.float() - ref).abs() <= tol).all(), kernel
