@@ -15,7 +15,13 @@ A from-scratch reimplementation of the capabilities of lucidrains/glom-pytorch
 """
 
 from glom_pytorch_amd.models.glom import Glom, GroupedFeedForward, ConsensusAttention
+from glom_pytorch_amd import islands
+from glom_pytorch_amd.islands import (edge_agreement, labels_from_agreement,
+                                      island_labels, island_sizes,
+                                      island_count)
 
 __version__ = "0.2.0"
 
-__all__ = ["Glom", "GroupedFeedForward", "ConsensusAttention"]
+__all__ = ["Glom", "GroupedFeedForward", "ConsensusAttention", "islands",
+           "edge_agreement", "labels_from_agreement", "island_labels",
+           "island_sizes", "island_count"]

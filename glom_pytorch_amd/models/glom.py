@@ -237,6 +237,16 @@ class Glom(nn.Module):
         self._graph_cache = None
         return self
 
+    def islands(self, levels: torch.Tensor, threshold: float = 0.9,
+                connectivity: int = 4) -> torch.Tensor:
+        """Island-of-agreement labels ``(*lead, L, side, side)`` of level
+        states ``(*lead, N, L, D)`` on this model's patch grid (see
+        ``glom_pytorch_amd.islands``); non-differentiable."""
+        from glom_pytorch_amd.islands import island_labels
+        side = self.num_patches_side
+        return island_labels(levels, threshold=threshold, grid=(side, side),
+                             connectivity=connectivity)
+
     # ------------------------------------------------------------------ #
     # Eager (plain PyTorch) path — the semantic specification. CPU tests
     # compare this against an independent loop-level oracle, and GPU tests

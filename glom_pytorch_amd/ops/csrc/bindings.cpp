@@ -15,6 +15,7 @@
 #include "gemm.h"
 #include "aux_kernels.h"
 #include "native_ops.h"
+#include "island_kernels.h"
 
 namespace {
 
@@ -1118,6 +1119,105 @@ void fused_adamw(std::vector<torch::Tensor> grads,
     check_launch();
 }
 
+// ------------------------------------------------------------------ //
+// island-of-agreement analysis (glom_pytorch_amd/islands.py): neighbour
+// cosine agreement on the patch grid and connected-component labels.
+// Inference-side analysis ops: no autograd, no host synchronisation.
+
+// levels (*lead, N, L, D) bf16 -> agreement (*lead, L, C, H, W) f32
+torch::Tensor island_agreement(torch::Tensor levels, int64_t H, int64_t W,
+                               int64_t connectivity) {
+    CHECK_IN(levels);
+    TORCH_CHECK(levels.dim() >= 3, "levels must be (*lead, N, L, D)");
+    TORCH_CHECK(connectivity == 4 || connectivity == 8,
+                "connectivity must be 4 or 8");
+    const int64_t nd = levels.dim();
+    const int64_t N = levels.size(nd - 3), L = levels.size(nd - 2),
+                  D = levels.size(nd - 1);
+    TORCH_CHECK(H > 0 && W > 0 && H * W == N, "grid does not match N");
+    TORCH_CHECK(D % 8 == 0, "dim must be a multiple of 8");
+    const int64_t C = connectivity == 4 ? 2 : 4;
+    TORCH_CHECK(N * L * C < (1LL << 30), "grid too large (32-bit indices)");
+    const int64_t P = N * L * D ? levels.numel() / (N * L * D) : 0;
+    // one wave per row, 4 per block; one thread per edge, 256 per block
+    TORCH_CHECK((P * N * L + 3) / 4 <= INT32_MAX
+                && (P * L * C * N + 255) / 256 <= INT32_MAX,
+                "too many rows for one launch");
+    std::vector<int64_t> shape(levels.sizes().begin(),
+                               levels.sizes().end() - 3);
+    shape.insert(shape.end(), {L, C, H, W});
+    auto fopts = levels.options().dtype(at::kFloat);
+    auto out = torch::empty(shape, fopts);
+    auto norm = torch::empty({P * L, N}, fopts);
+    hipStream_t s = cur_stream();
+    launch_island_dots(levels.data_ptr(), norm.data_ptr<float>(),
+                       out.data_ptr<float>(), P, (int)H, (int)W, (int)L,
+                       (int)D, (int)C, s);
+    check_launch();
+    launch_island_finish(norm.data_ptr<float>(), out.data_ptr<float>(),
+                         P * L, (int)H, (int)W, (int)C, s);
+    check_launch();
+    return out;
+}
+
+// agreement (*lead, L, C, H, W) f32 -> labels (*lead, L, H, W) i32
+torch::Tensor island_labels(torch::Tensor agreement, double threshold) {
+    TORCH_CHECK(agreement.is_cuda() && agreement.is_contiguous()
+                && agreement.scalar_type() == at::kFloat,
+                "agreement must be a contiguous f32 GPU tensor");
+    TORCH_CHECK(agreement.dim() >= 4,
+                "agreement must be (*lead, L, C, H, W)");
+    const int64_t nd = agreement.dim();
+    const int64_t C = agreement.size(nd - 3), H = agreement.size(nd - 2),
+                  W = agreement.size(nd - 1);
+    TORCH_CHECK(C == 2 || C == 4, "agreement must have 2 or 4 channels");
+    TORCH_CHECK(H * W <= ISLAND_MAX_CELLS, "native labelling needs N <= ",
+                ISLAND_MAX_CELLS);
+    const int64_t cell = C * H * W;
+    const int64_t PL = cell ? agreement.numel() / cell : 0;
+    TORCH_CHECK(PL <= INT32_MAX, "too many (lead, level) problems");
+    std::vector<int64_t> shape(agreement.sizes().begin(),
+                               agreement.sizes().end() - 3);
+    shape.insert(shape.end(), {H, W});
+    auto labels = torch::empty(shape, agreement.options().dtype(at::kInt));
+    launch_island_labels(agreement.data_ptr<float>(),
+                         labels.data_ptr<int>(), PL, (int)H, (int)W, (int)C,
+                         (float)threshold, cur_stream());
+    check_launch();
+    return labels;
+}
+
+// labels (*lead, H, W) i32 -> {sizes (*lead, H, W), count (*lead)} i32;
+// an output that is not wanted is neither allocated nor written (empty)
+std::vector<torch::Tensor> island_sizes(torch::Tensor labels,
+                                        bool want_sizes, bool want_count) {
+    TORCH_CHECK(labels.is_cuda() && labels.is_contiguous()
+                && labels.scalar_type() == at::kInt,
+                "labels must be a contiguous i32 GPU tensor");
+    TORCH_CHECK(labels.dim() >= 2, "labels must be (*lead, H, W)");
+    const int64_t nd = labels.dim();
+    const int64_t N = labels.size(nd - 2) * labels.size(nd - 1);
+    TORCH_CHECK(N <= ISLAND_MAX_CELLS, "native island sizes need N <= ",
+                ISLAND_MAX_CELLS);
+    TORCH_CHECK(N > 0, "empty grid");
+    const int64_t PL = labels.numel() / N;
+    TORCH_CHECK(PL <= INT32_MAX, "too many (lead, level) problems");
+    std::vector<int64_t> cshape(labels.sizes().begin(),
+                                labels.sizes().end() - 2);
+    auto sizes = want_sizes ? torch::empty_like(labels)
+                            : torch::empty({0}, labels.options());
+    auto count = want_count ? torch::empty(cshape, labels.options())
+                            : torch::empty({0}, labels.options());
+    if (want_sizes || want_count) {
+        launch_island_sizes(labels.data_ptr<int>(),
+                            want_sizes ? sizes.data_ptr<int>() : nullptr,
+                            want_count ? count.data_ptr<int>() : nullptr,
+                            PL, (int)N, cur_stream());
+        check_launch();
+    }
+    return {sizes, count};
+}
+
 std::string build_info() {
     return "glom_pytorch_amd HIP extension (gfx950, bf16 MFMA 16x16x32)";
 }
@@ -1171,6 +1271,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("set_nt8p", &set_nt8p, "toggle the 8-phase NT kernel (A/B)");
     m.def("set_gelu_pair", &set_gelu_pair,
           "toggle fused GELU-pair up-projection epilogue (A/B)");
+    m.def("island_agreement", &island_agreement,
+          "neighbour cosine agreement on the patch grid",
+          py::arg("levels"), py::arg("H"), py::arg("W"),
+          py::arg("connectivity"));
+    m.def("island_labels", &island_labels,
+          "connected components of the kept-edge graph (min-index labels)");
+    m.def("island_sizes", &island_sizes,
+          "island size at each root cell and/or island count",
+          py::arg("labels"), py::arg("want_sizes") = true,
+          py::arg("want_count") = true);
     m.def("build_info", &build_info);
     m.def("bench_gemm", &bench_gemm, "raw GEMM microbench (tuning only)");
 }
