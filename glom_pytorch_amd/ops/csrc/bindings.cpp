@@ -69,6 +69,91 @@ int g_gelu_pair = []() {
 }();
 void set_gelu_pair(bool on) { g_gelu_pair = on ? 1 : 0; }
 
+// Register-epilogue width of the nt5p kernel: the rounded bf16 values can
+// be transposed in registers and moved as 16-byte accesses instead of the
+// 2-byte fragment-order ones; bitwise identical results either way.
+//   0 = narrow everywhere (GLOM_WIDE_EPI=0)
+//   1 = per epilogue, what measured faster (default; wide_epi_auto below)
+//   2 = wide everywhere: stores and aux loads
+//   3 = wide aux loads, narrow stores
+// set_wide_epilogue(bool) picks 2 / 0 and set_wide_epilogue_mode(int) any
+// of them, for within-process A/B (scripts/wide_epi_ab.py) and the tests.
+int g_wide_epi = []() {
+    const char* e = getenv("GLOM_WIDE_EPI");
+    return (e && e[0] >= '0' && e[0] <= '3') ? e[0] - '0' : 1;
+}();
+// nt8p has its own switch: its tail is a smaller share of a K >= 2048
+// tile, so it is judged (and defaulted) separately (GLOM_WIDE_EPI_NT8P)
+int g_wide_epi_nt8p = []() {
+    const char* e = getenv("GLOM_WIDE_EPI_NT8P");
+    return (e && e[0] == '1') ? 1 : 0;
+}();
+void set_wide_epilogue(bool on) { g_wide_epi = on ? 2 : 0; }
+void set_wide_epilogue_mode(int64_t m) {
+    TORCH_CHECK(m >= 0 && m <= 3, "wide epilogue mode is 0..3");
+    g_wide_epi = (int)m;
+}
+int64_t get_wide_epilogue_mode() { return g_wide_epi; }
+// Default policy, from the op-level A/B at the headline shapes
+// (profiles/wide_epilogue_ab.txt): dH gains from the early 16-byte aux
+// loads, the single-output EPI_GELU a little from wide stores; with two
+// output streams (EPI_GELU_PAIR) the wide stores measured no gain, with a
+// plain C ~2% slower than the 2-byte ones, so both stay off.
+static int wide_epi_auto(int epilogue) {
+    return epilogue == EPI_GELUGRAD ? 3 : epilogue == EPI_GELU ? 1 : 0;
+}
+// GemmParams::wide_epi bits (1 = stores, 2 = aux loads) for nt5p
+static int nt5p_wide_bits(int epilogue) {
+    switch (g_wide_epi) {
+    case 0: return 0;
+    case 2: return 3;
+    case 3: return 2;
+    default: return wide_epi_auto(epilogue);
+    }
+}
+void set_wide_epilogue_nt8p(bool on) { g_wide_epi_nt8p = on ? 1 : 0; }
+
+// 16-byte accesses need 16-byte-aligned bases and row / problem strides
+// that are multiples of 8 bf16 elements
+static bool wide_epi_ok(const GemmParams& p) {
+    auto al = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
+    bool ok = al(p.Cbase) && p.Cld % 8 == 0 && p.Csin % 8 == 0
+              && p.Csout % 8 == 0;
+    if (p.epilogue == EPI_GELU_PAIR)
+        ok = ok && al(p.out2) && p.out2_ld % 8 == 0 && p.out2_sin % 8 == 0
+             && p.out2_sout % 8 == 0;
+    if (p.epilogue == EPI_GELUGRAD)
+        ok = ok && al(p.aux_base) && p.aux_ld % 8 == 0 && p.aux_sin % 8 == 0
+             && p.aux_sout % 8 == 0;
+    return ok;
+}
+
+// persistent continuous-ring variant (default ON; opt out with
+// GLOM_NT5P=0): one block sweeps 4 M-tiles of a column, register
+// epilogue in the shadow of the next tile's MFMAs, fused colsum kept
+static bool nt5p_enabled() {
+    static const bool on = []() {
+        const char* e = getenv("GLOM_NT5P");
+        return !e || e[0] != '0';
+    }();
+    return on;
+}
+static long nt5p_min_grid() {
+    static const long g = []() {
+        const char* e = getenv("GLOM_NT5P_MING");
+        return e ? atol(e) : 96;
+    }();
+    return g;
+}
+// Will run_gemm route this up-projection (bf16 NT, contiguous operands,
+// plain C) to nt5p? Mirrors run_gemm's conditions for that shape family;
+// run_gemm itself rejects EPI_GELU if the two ever disagree.
+static bool nt5p_takes_up_proj(int64_t M, int64_t N, int64_t K, int64_t G) {
+    return nt5p_enabled() && M % 512 == 0 && N % 256 == 0 && N >= 1024
+           && K % 64 == 0 && K >= 64
+           && (N / 256) * (M / 512) * G >= nt5p_min_grid();
+}
+
 void check_launch() {
     hipError_t e = hipGetLastError();
     TORCH_CHECK(e == hipSuccess, "HIP launch failed: ", hipGetErrorString(e));
@@ -108,30 +193,26 @@ void run_gemm(GemmParams& p, hipStream_t s, const torch::TensorOptions& opts,
         }
     }
     const bool nt3 = nt_fast && p.N % 256 == 0 && p.N >= 1024;
-    // persistent continuous-ring variant (default ON; opt out with
-    // GLOM_NT5P=0): one block sweeps 4 M-tiles of a column, register
-    // epilogue in the shadow of the next tile's MFMAs, fused colsum kept
-    static const bool nt5p_on = []() {
-        const char* e = getenv("GLOM_NT5P");
-        return !e || e[0] != '0';
-    }();
+    const bool nt5p_on = nt5p_enabled();
     // N >= 1024 only: at N=512 (2 column panels) the persistent sweep
     // measured SLOWER than the 128^2 kernel on the down-projection
     // (637 -> 573 TF), so that shape keeps nt_fast
     // >= 96 (was 256): at the small-batch inference shapes (video B=8:
     // 192-block grids) the persistent sweep beats nt3 by ~20% (3172 ->
     // 3812 frames/s); training grids are >= 768 and unaffected.
-    static const long nt5p_ming = []() {
-        const char* e = getenv("GLOM_NT5P_MING");
-        return e ? atol(e) : 96;
-    }();
     const bool nt5p = nt5p_on && nt3 && p.M % 512 == 0
                       && (long)(p.N / 256) * (p.M / 512) * p.nproblems
-                         >= nt5p_ming
+                         >= nt5p_min_grid()
                       && !(p.Cflags & OP_TABLE)
                       && (p.epilogue == EPI_NONE
                           || p.epilogue == EPI_GELUGRAD
-                          || p.epilogue == EPI_GELU_PAIR);
+                          || p.epilogue == EPI_GELU_PAIR
+                          || p.epilogue == EPI_GELU);
+    // only nt5p's register epilogue implements EPI_GELU; callers ask
+    // nt5p_takes_up_proj() first and keep EPI_GELU_PAIR / the standalone
+    // gelu pass otherwise
+    TORCH_CHECK(p.epilogue != EPI_GELU || nt5p,
+                "EPI_GELU needs an nt5p-eligible shape");
     static const bool disp_dbg = []() {
         const char* e = getenv("GLOM_DISPATCH_DEBUG");
         return e && e[0] == '1';
@@ -155,6 +236,8 @@ void run_gemm(GemmParams& p, hipStream_t s, const torch::TensorOptions& opts,
                       && (p.epilogue == EPI_NONE
                           || p.epilogue == EPI_GELUGRAD)
                       && (long)(p.N / 256) * (p.M / 256) * p.nproblems >= 256;
+    p.wide_epi = !wide_epi_ok(p) ? 0
+                 : nt8p ? g_wide_epi_nt8p : nt5p_wide_bits(p.epilogue);
     if (disp_dbg)
         fprintf(stderr,
                 "[dispatch] L%d M%ld N%ld K%ld epi%d nt3=%d nt5p=%d on=%d "
@@ -205,7 +288,8 @@ GemmParams base_params(int64_t M, int64_t N, int64_t K, int layout,
 std::vector<torch::Tensor> grouped_ff_fwd(
         c10::optional<torch::Tensor> tokens_opt, torch::Tensor levels,
         c10::optional<torch::Tensor> pos_opt, torch::Tensor w1,
-        torch::Tensor b1, torch::Tensor w2, torch::Tensor b2, int64_t mode) {
+        torch::Tensor b1, torch::Tensor w2, torch::Tensor b2, int64_t mode,
+        bool save_for_bwd = true) {
     CHECK_IN(levels); CHECK_IN(w1); CHECK_IN(b1); CHECK_IN(w2); CHECK_IN(b2);
     const int64_t B = levels.size(0), N = levels.size(1),
                   L = levels.size(2), d = levels.size(3);
@@ -218,7 +302,17 @@ std::vector<torch::Tensor> grouped_ff_fwd(
     TORCH_CHECK(w2.size(0) == G * d && w2.size(1) == m4);
 
     auto opts = levels.options();
-    auto Hpre = torch::empty({G, M, m4}, opts);
+    const bool pair = g_gelu_pair
+                      && (M % 512 == 0) && (m4 % 256 == 0)
+                      && m4 >= 1024;   // nt5p-eligible shapes only
+    // forward-only callers (save_for_bwd == false) never read the
+    // pre-activation (only the backward's gelu' does): where nt5p serves
+    // the up-projection it writes gelu(pre-act) alone (EPI_GELU) and Hpre
+    // is neither allocated nor written
+    const bool gelu_only = !save_for_bwd && pair
+                           && nt5p_takes_up_proj(M, m4, d, G);
+    auto Hpre = gelu_only ? torch::empty({0}, opts)
+                          : torch::empty({G, M, m4}, opts);
     auto Hact = torch::empty({G, M, m4}, opts);
     auto Y = torch::empty({B, N, G, d}, opts);
     hipStream_t s = cur_stream();
@@ -257,10 +351,10 @@ std::vector<torch::Tensor> grouped_ff_fwd(
         p.B.base = w1.data_ptr(); p.B.sin = m4 * d; p.B.ld = d;
         p.Cbase = Hpre.data_ptr(); p.Csin = M * m4; p.Cld = m4;
         p.bias_base = b1.data_ptr(); p.bias_sin = m4; p.has_bias = 1;
-        const bool pair = g_gelu_pair
-                          && (M % 512 == 0) && (m4 % 256 == 0)
-                          && m4 >= 1024;   // nt5p-eligible shapes only
-        if (pair) {
+        if (gelu_only) {
+            p.epilogue = EPI_GELU;
+            p.Cbase = Hact.data_ptr();
+        } else if (pair) {
             p.epilogue = EPI_GELU_PAIR;
             p.out2 = Hact.data_ptr();
             p.out2_sin = M * m4; p.out2_ld = m4;
@@ -282,6 +376,7 @@ std::vector<torch::Tensor> grouped_ff_fwd(
         run_gemm(p, s, opts, true);
     }
     if (mode != 1) td_in = torch::empty({0}, opts);
+    if (!save_for_bwd) Hpre = torch::empty({0}, opts);
     // td_in returned so the backward reuses it (saves re-running
     // k_add_pos per iteration in the weight-grad GEMM)
     return {Y, Hpre, Hact, td_in};
@@ -684,11 +779,11 @@ std::vector<torch::Tensor> glom_step_fwd(
         torch::Tensor tw2, torch::Tensor tb2, bool attend_self,
         c10::optional<torch::Tensor> mask,
         c10::optional<torch::Tensor> slab = c10::nullopt,
-        int64_t slab_idx = 0) {
+        int64_t slab_idx = 0, bool save_for_bwd = true) {
     auto bu = grouped_ff_fwd(tokens, levels, c10::nullopt, bw1, bb1, bw2,
-                             bb2, 0);
+                             bb2, 0, save_for_bwd);
     auto td = grouped_ff_fwd(c10::nullopt, levels, pos, tw1, tb1, tw2,
-                             tb2, 1);
+                             tb2, 1, save_for_bwd);
     auto at = consensus_fwd(levels, attend_self, mask);
     auto out = level_mix_fwd(levels, bu[0], td[0], at[0], slab, slab_idx);
     return {out, bu[1], bu[2], td[1], td[2], at[1], at[2], td[3]};
@@ -765,7 +860,8 @@ double bench_gemm(int64_t M, int64_t N, int64_t K, int64_t layout,
         if (epilogue == EPI_GELUGRAD) {
             p.aux_base = aux.data_ptr(); p.aux_sin = M * N; p.aux_ld = N;
         }
-        if (epilogue == EPI_GELU_PAIR || epilogue == 10 || epilogue == 12) {
+        if (epilogue == EPI_GELU_PAIR || epilogue == EPI_GELU
+            || epilogue == 10 || epilogue == 12) {
             p.bias_base = bias.data_ptr(); p.bias_sin = N; p.has_bias = 1;
             p.out2 = out2.data_ptr(); p.out2_sin = M * N; p.out2_ld = N;
         }
@@ -1225,7 +1321,10 @@ std::string build_info() {
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
-    m.def("grouped_ff_fwd", &grouped_ff_fwd, "grouped FF forward");
+    m.def("grouped_ff_fwd", &grouped_ff_fwd, "grouped FF forward",
+          py::arg("tokens"), py::arg("levels"), py::arg("pos"),
+          py::arg("w1"), py::arg("b1"), py::arg("w2"), py::arg("b2"),
+          py::arg("mode"), py::arg("save_for_bwd") = true);
     m.def("grouped_ff_bwd", &grouped_ff_bwd, "grouped FF backward",
           py::arg("dY"), py::arg("tokens"), py::arg("levels"),
           py::arg("pos"), py::arg("w1"), py::arg("w2"),
@@ -1244,7 +1343,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("bw1"), py::arg("bb1"), py::arg("bw2"), py::arg("bb2"),
           py::arg("tw1"), py::arg("tb1"), py::arg("tw2"), py::arg("tb2"),
           py::arg("attend_self"), py::arg("mask"),
-          py::arg("slab") = c10::nullopt, py::arg("slab_idx") = 0);
+          py::arg("slab") = c10::nullopt, py::arg("slab_idx") = 0,
+          py::arg("save_for_bwd") = true);
     m.def("glom_step_bwd", &glom_step_bwd, "full GLOM iteration backward",
           py::arg("dnew"), py::arg("tokens"), py::arg("levels"),
           py::arg("pos"), py::arg("bw1"), py::arg("bw2"), py::arg("tw1"),
@@ -1269,6 +1369,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("Hact"), py::arg("mode"),
           py::arg("td_in") = c10::nullopt);
     m.def("set_nt8p", &set_nt8p, "toggle the 8-phase NT kernel (A/B)");
+    m.def("set_wide_epilogue", &set_wide_epilogue,
+          "toggle the 16-byte register epilogue of nt5p (A/B)");
+    m.def("set_wide_epilogue_mode", &set_wide_epilogue_mode,
+          "0 narrow, 1 per-epilogue default, 2 all wide, 3 wide aux only");
+    m.def("get_wide_epilogue_mode", &get_wide_epilogue_mode);
+    m.def("set_wide_epilogue_nt8p", &set_wide_epilogue_nt8p,
+          "toggle the 16-byte register epilogue of nt8p (A/B)");
     m.def("set_gelu_pair", &set_gelu_pair,
           "toggle fused GELU-pair up-projection epilogue (A/B)");
     m.def("island_agreement", &island_agreement,

@@ -12,6 +12,9 @@ enum GemmEpilogue {
     // full-row fusions (tile spans the whole row, nt_fast3 only):
     EPI_SOFTMAX = 3,   // consensus scores -> masked row softmax -> P
     EPI_SMBWD = 4,     // dP -> row softmax backward -> dS (C), dSr (out2)
+    // C = gelu(bf16(acc*alpha + bias)): EPI_GELU_PAIR's out2 without the
+    // pre-activation (forward-only steps; nt5p only, see run_gemm)
+    EPI_GELU = 5,
 };
 
 #define GEMM_MAX_TABLE 16
@@ -72,6 +75,12 @@ struct GemmParams {
     // host-verified: every A/B row stride is a multiple of 8 elements and
     // tiles are full -> the glds/repack fast kernels may run
     int fast_ok;
+
+    // host-verified: C / out2 / aux bases are 16-byte aligned and their row
+    // strides multiples of 8 elements -> the register epilogues of nt5p
+    // and nt8p may use 16-byte accesses (set by run_gemm): bit 0 = C/out2
+    // stores, bit 1 = aux loads
+    int wide_epi;
 
     const void* Atab[GEMM_MAX_TABLE]; long Atabld[GEMM_MAX_TABLE];
     const void* Btab[GEMM_MAX_TABLE]; long Btabld[GEMM_MAX_TABLE];

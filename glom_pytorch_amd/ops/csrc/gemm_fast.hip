@@ -1212,17 +1212,133 @@ void launch_gemm_nt_fast4(const GemmParams& p, hipStream_t stream) {
 }
 
 
+// ------- wide register epilogue (shared by nt5p and nt8p) -------
+// The MFMA C fragment of a 16x64 wave slab puts, in lane (kq, lrow),
+// register r of fragment j16 at row 4*kq+r, column j16*16+lrow: stored
+// directly that is one 2-byte access per lane and value. These helpers
+// re-lay out the ALREADY ROUNDED bf16 values (pure data movement, so every
+// stored bit and the f32 column sums are untouched) into 16 contiguous
+// bytes per lane:
+//   1. quad transpose (2 DPP quad_perm + 4 v_perm per fragment): lane
+//      lrow = 4c+q trades its 4 rows of one column for row 4*kq+q,
+//      columns 4c..4c+3 (the transpose is its own inverse);
+//   2. lane-xor-4 exchange across a fragment pair (2P, 2P+1) (row_shr:4 /
+//      row_shl:4 with a bank mask, 2 DPP per dword): even c keeps fragment
+//      2P and receives lane c+1's half of it, odd c the same for 2P+1.
+// Lane (kq, 4c+q) then owns row 4*kq+q, slab columns
+// (2P + (c&1))*16 + (c>>1)*8 .. +7: one 16-byte access per (lane, P), 8 per
+// 128x256-tile output instead of 64. The reverse direction turns 16-byte
+// loads of the aux operand back into the fragment layout.
+struct WideEpi {
+    unsigned selA, selB, sel0, sel1;   // per-lane v_perm selectors
+    bool qhi;                          // lane's q has bit 1 set
+    int row;                           // row within the 16-row slab
+    int col0;                          // slab column of pair 0's 8 values
+    __device__ __forceinline__ WideEpi(int lane) {
+        const int q = lane & 3, c = (lane >> 2) & 3;
+        qhi = q & 2;
+        selA = (q & 1) ? 0x05040100u : 0x07060302u;
+        selB = (q & 1) ? 0x07060302u : 0x05040100u;
+        sel0 = q == 0 ? 0x01000504u : q == 1 ? 0x05040100u
+             : q == 2 ? 0x03020706u : 0x07060302u;
+        sel1 = q == 0 ? 0x03020706u : q == 1 ? 0x07060302u
+             : q == 2 ? 0x01000504u : 0x05040100u;
+        row = (lane >> 4) * 4 + q;
+        col0 = (c & 1) * 16 + (c >> 1) * 8;
+    }
+    // 4x4 transpose of 16-bit values across a lane quad. In: p0 = regs
+    // (0,1), p1 = regs (2,3) packed low|high. Out: d0 = (0,1), d1 = (2,3)
+    // of the transposed matrix.
+    __device__ __forceinline__ void quad_tr(unsigned p0, unsigned p1,
+                                            unsigned& d0, unsigned& d1) const {
+        unsigned send = qhi ? p0 : p1, keep = qhi ? p1 : p0;
+        unsigned recv = __builtin_amdgcn_mov_dpp(send, 0x4E, 0xf, 0xf, true);
+        unsigned send2 = __builtin_amdgcn_perm(recv, keep, selA);
+        unsigned own2 = __builtin_amdgcn_perm(recv, keep, selB);
+        unsigned rb = __builtin_amdgcn_mov_dpp(send2, 0xB1, 0xf, 0xf, true);
+        d0 = __builtin_amdgcn_perm(own2, rb, sel0);
+        d1 = __builtin_amdgcn_perm(own2, rb, sel1);
+    }
+    // fragment -> rows: v[r][j16] (bf16 bits) -> out[P], P = 0,1
+    __device__ __forceinline__ void to_rows(const ushort_t v[4][4],
+                                            uint4v out[2]) const {
+        unsigned d0[4], d1[4];
+#pragma unroll
+        for (int j = 0; j < 4; j++)
+            quad_tr(v[0][j] | ((unsigned)v[1][j] << 16),
+                    v[2][j] | ((unsigned)v[3][j] << 16), d0[j], d1[j]);
+#pragma unroll
+        for (int P = 0; P < 2; P++) {
+            const int e = 2 * P, o = 2 * P + 1;
+            // low 8 bytes: own even fragment / lane-4's odd fragment;
+            // high 8 bytes: lane+4's even fragment / own odd fragment
+            out[P][0] = __builtin_amdgcn_update_dpp(d0[e], d0[o], 0x114,
+                                                    0xf, 0xA, false);
+            out[P][1] = __builtin_amdgcn_update_dpp(d1[e], d1[o], 0x114,
+                                                    0xf, 0xA, false);
+            out[P][2] = __builtin_amdgcn_update_dpp(d0[o], d0[e], 0x104,
+                                                    0xf, 0x5, false);
+            out[P][3] = __builtin_amdgcn_update_dpp(d1[o], d1[e], 0x104,
+                                                    0xf, 0x5, false);
+        }
+    }
+    // `p` = this lane's (row, col0) element of the slab in a row-major
+    // bf16 matrix, 16-byte aligned: two 16-byte accesses per lane and slab
+    __device__ __forceinline__ void store(ushort_t* p,
+                                          const ushort_t v[4][4]) const {
+        uint4v w[2];
+        to_rows(v, w);
+        *(uint4v*)p = w[0];
+        *(uint4v*)(p + 32) = w[1];
+    }
+    __device__ __forceinline__ void load(const ushort_t* p,
+                                         uint4v w[2]) const {
+        w[0] = *(const uint4v*)p;
+        w[1] = *(const uint4v*)(p + 32);
+    }
+    // rows -> fragment (inverse of to_rows)
+    __device__ __forceinline__ void to_frag(const uint4v in[2],
+                                            ushort_t v[4][4]) const {
+#pragma unroll
+        for (int P = 0; P < 2; P++) {
+            unsigned de0 = __builtin_amdgcn_update_dpp(in[P][0], in[P][2],
+                                                       0x114, 0xf, 0xA, false);
+            unsigned de1 = __builtin_amdgcn_update_dpp(in[P][1], in[P][3],
+                                                       0x114, 0xf, 0xA, false);
+            unsigned do0 = __builtin_amdgcn_update_dpp(in[P][2], in[P][0],
+                                                       0x104, 0xf, 0x5, false);
+            unsigned do1 = __builtin_amdgcn_update_dpp(in[P][3], in[P][1],
+                                                       0x104, 0xf, 0x5, false);
+            unsigned p0, p1;
+            quad_tr(de0, de1, p0, p1);
+            v[0][2 * P] = (ushort_t)p0; v[1][2 * P] = (ushort_t)(p0 >> 16);
+            v[2][2 * P] = (ushort_t)p1; v[3][2 * P] = (ushort_t)(p1 >> 16);
+            quad_tr(do0, do1, p0, p1);
+            v[0][2 * P + 1] = (ushort_t)p0;
+            v[1][2 * P + 1] = (ushort_t)(p0 >> 16);
+            v[2][2 * P + 1] = (ushort_t)p1;
+            v[3][2 * P + 1] = (ushort_t)(p1 >> 16);
+        }
+    }
+};
+
+
 // ------- persistent continuous-ring NT variant (nt5p) -------
 // Each block sweeps PERSIST consecutive 128-row M-tiles of ONE 256-col
 // N-column. The 3-ring never drains at tile boundaries (the global step
 // stream g = tile*nk + kt staggers straight across tiles), so the per-tile
 // prologue cost — ~50% of a K=512 block in nt4 (profiles/README
 // K-amortization) — is paid once per PERSIST tiles. The epilogue runs from
-// registers (scalar stores; no LDS image — the ring owns the arena) in the
-// shadow of the next tile's MFMAs. Supports alpha/bias/colscale/GELUGRAD
-// and the fused f32 colsum (one partial store per wave half/column/tile); no
-// softmax/pair/table-C epilogues — the dispatcher routes those to nt4.
-template <int PERSIST>
+// registers (no LDS image — the ring owns the arena) in the shadow of the
+// next tile's MFMAs: 2-byte fragment-order accesses, or, per the WIDE
+// template bits, 16-byte ones after an in-register transpose (WideEpi).
+// Supports alpha/bias/colscale, GELUGRAD, GELU_PAIR, GELU and the fused f32
+// colsum (one partial store per wave half/column/tile); no softmax/table-C
+// epilogues — the dispatcher routes those to nt4.
+// WIDE (GemmParams::wide_epi): bit 0 = 16-byte C / out2 stores, bit 1 =
+// 16-byte aux loads issued ahead of the tile-end MFMAs; 0 = the 2-byte
+// fragment-order epilogue. All give identical bits.
+template <int PERSIST, int WIDE>
 __global__ __launch_bounds__(NT3) void gemm_nt_fast5p_kernel(GemmParams p) {
     __shared__ ushort_t smem[3 * (128 + 256) * FBK];   // 144 KiB, 3-ring
     const int abuf = 128 * FBK, bbuf = 256 * FBK, stride = abuf + bbuf;
@@ -1276,6 +1392,8 @@ __global__ __launch_bounds__(NT3) void gemm_nt_fast5p_kernel(GemmParams p) {
     if (p.epilogue == EPI_GELU_PAIR && p.out2)
         o2p = (ushort_t*)p.out2 + (long)(pid % p.nInner) * p.out2_sin
               + (long)(pid / p.nInner) * p.out2_sout;
+    // EPI_GELU: C itself gets gelu(bf16 pre-act), the pre-act is not kept
+    const bool gelu_c = p.epilogue == EPI_GELU;
 
     const int wid = threadIdx.x / WAVE;
     const int lane = threadIdx.x % WAVE;
@@ -1283,6 +1401,7 @@ __global__ __launch_bounds__(NT3) void gemm_nt_fast5p_kernel(GemmParams p) {
     const int wn = (wid & 3) * 64;
     const int lrow = lane & 15;
     const int kq = lane >> 4;
+    const WideEpi we(lane);
 
     float csv[4] = {1.f, 1.f, 1.f, 1.f};
     float bvv[4] = {0.f, 0.f, 0.f, 0.f};
@@ -1346,6 +1465,23 @@ __global__ __launch_bounds__(NT3) void gemm_nt_fast5p_kernel(GemmParams p) {
         // glds in flight. Stores retire once their data leaves the VGPRs
         // (no memory round trip), so that wait stays cheap.
         if (!tile_end && g + 2 < TOT) stage_g((g + 2) % 3, g + 2);
+        // Wide epilogue, EPI_GELUGRAD: all 8 16-byte aux loads of this tile
+        // go out here, ahead of the step's MFMAs, which hide their latency.
+        // Issue order at a tile_end step is then [g+1 glds (previous
+        // step), aux loads, C stores, g+2 glds]: the compiler's wait for
+        // the aux data retires g+1's glds a little early (they were issued
+        // a whole step ago), and the bottom vmcnt(6) still covers
+        // everything up to the stores and leaves exactly g+2's 6 glds in
+        // flight, as before.
+        uint4v auxw[4][2];
+        if ((WIDE & 2) && tile_end && auxp) {
+            const ushort_t* abase =
+                auxp + (m0 + (long)(g / nk) * BM + wm + we.row) * p.aux_ld
+                + n0 + wn + we.col0;
+#pragma unroll
+            for (int i16 = 0; i16 < 4; i16++)
+                we.load(abase + (long)(i16 * 16) * p.aux_ld, auxw[i16]);
+        }
         const ushort_t* Al = smem + (g % 3) * stride;
         const ushort_t* Bl = Al + abuf;
         short8 af[2][4], bfr[2][4];
@@ -1378,6 +1514,92 @@ __global__ __launch_bounds__(NT3) void gemm_nt_fast5p_kernel(GemmParams p) {
             // next tile
             const long mt0 = m0 + (long)(g / nk) * BM;
             float colacc[4] = {0.f, 0.f, 0.f, 0.f};
+            if constexpr (WIDE) {
+                // same arithmetic, same (i16, r) order into colacc as the
+                // narrow path below; only the rounded bf16 values are
+                // re-laid out (WideEpi) so each lane moves 16 bytes
+#pragma unroll
+                for (int i16 = 0; i16 < 4; i16++) {
+                    ushort_t avv[4][4], cbv[4][4], obv[4][4];
+                    if (auxp) {
+                        if constexpr (WIDE & 2) {
+                            we.to_frag(auxw[i16], avv);
+                        } else {
+                            const ushort_t* ap =
+                                auxp + (mt0 + wm + i16 * 16 + kq * 4)
+                                       * p.aux_ld + n0 + wn + lrow;
+#pragma unroll
+                            for (int r = 0; r < 4; r++)
+#pragma unroll
+                                for (int j16 = 0; j16 < 4; j16++)
+                                    avv[r][j16] =
+                                        ap[r * p.aux_ld + j16 * 16];
+                        }
+                    }
+#pragma unroll
+                    for (int r = 0; r < 4; r++) {
+                        float vv[4];
+#pragma unroll
+                        for (int j16 = 0; j16 < 4; j16++)
+                            vv[j16] = acc[i16][j16][r] * p.alpha * csv[j16];
+                        if (auxp) {
+                            float gx[4], gy[4];
+#pragma unroll
+                            for (int j16 = 0; j16 < 4; j16++)
+                                gx[j16] = bf2f(avv[r][j16]);
+                            gelu_grad_vec<4>(gx, gy);
+#pragma unroll
+                            for (int j16 = 0; j16 < 4; j16++)
+                                vv[j16] *= gy[j16];
+                        }
+#pragma unroll
+                        for (int j16 = 0; j16 < 4; j16++) {
+                            ushort_t cb = f2bf(vv[j16] + bvv[j16]);
+                            colacc[j16] += bf2f(cb);
+                            cbv[r][j16] = cb;
+                        }
+                        if (o2p || gelu_c) {
+                            float gx[4], gy[4];
+#pragma unroll
+                            for (int j16 = 0; j16 < 4; j16++)
+                                gx[j16] = bf2f(cbv[r][j16]);
+                            gelu_f_vec<4>(gx, gy);
+#pragma unroll
+                            for (int j16 = 0; j16 < 4; j16++)
+                                obv[r][j16] = f2bf(gy[j16]);
+                        }
+                        acc[i16][0][r] = 0.f; acc[i16][1][r] = 0.f;
+                        acc[i16][2][r] = 0.f; acc[i16][3][r] = 0.f;
+                    }
+                    if constexpr (WIDE & 1) {
+                        const long gi = mt0 + wm + i16 * 16 + we.row;
+                        const long cj = n0 + wn + we.col0;
+                        if (!gelu_c) we.store(Cp + gi * ldc + cj, cbv);
+                        if (o2p || gelu_c)
+                            we.store(gelu_c ? Cp + gi * ldc + cj
+                                            : o2p + gi * p.out2_ld + cj,
+                                     obv);
+                    } else {
+                        // wide aux loads only: fragment-order stores
+                        const long gi = mt0 + wm + i16 * 16 + kq * 4;
+                        const long cj = n0 + wn + lrow;
+#pragma unroll
+                        for (int r = 0; r < 4; r++)
+#pragma unroll
+                            for (int j16 = 0; j16 < 4; j16++) {
+                                if (!gelu_c)
+                                    Cp[(gi + r) * ldc + cj + j16 * 16] =
+                                        cbv[r][j16];
+                                if (gelu_c)
+                                    Cp[(gi + r) * ldc + cj + j16 * 16] =
+                                        obv[r][j16];
+                                else if (o2p)
+                                    o2p[(gi + r) * p.out2_ld + cj
+                                        + j16 * 16] = obv[r][j16];
+                            }
+                    }
+                }
+            } else {
 #pragma unroll
             for (int i16 = 0; i16 < 4; i16++) {
 #pragma unroll
@@ -1411,9 +1633,9 @@ __global__ __launch_bounds__(NT3) void gemm_nt_fast5p_kernel(GemmParams p) {
                         // per summand (only the fixed add order differs)
                         colacc[j16] += bf2f(cb);
                         cbv[j16] = cb;
-                        crow[j16 * 16] = cb;
+                        if (!gelu_c) crow[j16 * 16] = cb;
                     }
-                    if (o2p) {
+                    if (o2p || gelu_c) {
                         // gelu of the bf16-rounded pre-activation:
                         // bitwise the standalone k_gelu pass
                         float gx[4], gy[4];
@@ -1421,8 +1643,9 @@ __global__ __launch_bounds__(NT3) void gemm_nt_fast5p_kernel(GemmParams p) {
                         for (int j16 = 0; j16 < 4; j16++)
                             gx[j16] = bf2f(cbv[j16]);
                         gelu_f_vec<4>(gx, gy);
-                        ushort_t* orow = o2p + gi * p.out2_ld + n0 + wn
-                                         + lrow;
+                        ushort_t* orow = gelu_c
+                            ? crow
+                            : o2p + gi * p.out2_ld + n0 + wn + lrow;
 #pragma unroll
                         for (int j16 = 0; j16 < 4; j16++)
                             orow[j16 * 16] = f2bf(gy[j16]);
@@ -1430,6 +1653,7 @@ __global__ __launch_bounds__(NT3) void gemm_nt_fast5p_kernel(GemmParams p) {
                     acc[i16][0][r] = 0.f; acc[i16][1][r] = 0.f;
                     acc[i16][2][r] = 0.f; acc[i16][3][r] = 0.f;
                 }
+            }
             }
             if (colp) {
                 // this wave's 64 rows: fold the 4 kq lane groups, one store
@@ -1464,15 +1688,30 @@ void launch_gemm_nt_fast5p(const GemmParams& p, hipStream_t stream) {
     const int P = (pref == 8 && p.M % (BM * 8) == 0) ? 8
                 : (pref == 2) ? 2 : 4;
     dim3 grid(p.N / BN3, p.M / (BM * P), p.nproblems);
+    // without an aux operand bit 1 means nothing; wide stores with narrow
+    // aux loads (1) is not built: nothing measured in its favour
+    const bool has_aux = p.epilogue == EPI_GELUGRAD;
+    const int wide = !has_aux ? ((p.wide_epi & 1) ? 3 : 0)
+                   : (p.wide_epi & 2) ? (p.wide_epi & 3) : 0;
+#define NT5P_LAUNCH(PP)                                                     \
+    do {                                                                    \
+        if (wide == 3)                                                      \
+            hipLaunchKernelGGL((gemm_nt_fast5p_kernel<PP, 3>), grid,        \
+                               dim3(NT3), 0, stream, p);                    \
+        else if (wide == 2)                                                 \
+            hipLaunchKernelGGL((gemm_nt_fast5p_kernel<PP, 2>), grid,        \
+                               dim3(NT3), 0, stream, p);                    \
+        else                                                                \
+            hipLaunchKernelGGL((gemm_nt_fast5p_kernel<PP, 0>), grid,        \
+                               dim3(NT3), 0, stream, p);                    \
+    } while (0)
     if (P == 8)
-        hipLaunchKernelGGL(gemm_nt_fast5p_kernel<8>, grid, dim3(NT3), 0,
-                           stream, p);
+        NT5P_LAUNCH(8);
     else if (P == 2)
-        hipLaunchKernelGGL(gemm_nt_fast5p_kernel<2>, grid, dim3(NT3), 0,
-                           stream, p);
+        NT5P_LAUNCH(2);
     else
-        hipLaunchKernelGGL(gemm_nt_fast5p_kernel<4>, grid, dim3(NT3), 0,
-                           stream, p);
+        NT5P_LAUNCH(4);
+#undef NT5P_LAUNCH
 }
 
 
@@ -1500,6 +1739,7 @@ void launch_gemm_nt_fast5p(const GemmParams& p, hipStream_t stream) {
 #define BN8 256
 #define NT8 512
 
+template <bool WIDE>
 __global__ __launch_bounds__(NT8) void gemm_nt_fast8p_kernel(GemmParams p) {
     __shared__ ushort_t smem[2 * (BM8 + BN8) * FBK];   // 128 KiB
     const int abuf = BM8 * FBK, stride = (BM8 + BN8) * FBK;
@@ -1674,6 +1914,48 @@ __global__ __launch_bounds__(NT8) void gemm_nt_fast8p_kernel(GemmParams p) {
 
     // ------------- register epilogue (mirrors nt5p, 8 mfrags) ----------
     float colacc[4] = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (WIDE) {
+        // nt5p's wide epilogue; the accumulators fill the register file
+        // here, so aux is fetched one 16-row slab ahead, not a tile ahead
+        const WideEpi we(lane);
+        const long gi0 = (long)m0 + wm + we.row;
+        const long cj = n0 + wn + we.col0;
+        uint4v auxw[2][2];
+        if (auxp) we.load(auxp + gi0 * p.aux_ld + cj, auxw[0]);
+#pragma unroll
+        for (int i16 = 0; i16 < 8; i16++) {
+            ushort_t avv[4][4], cbv[4][4];
+            if (auxp) {
+                if (i16 + 1 < 8)
+                    we.load(auxp + (gi0 + (i16 + 1) * 16) * p.aux_ld + cj,
+                            auxw[(i16 + 1) & 1]);
+                we.to_frag(auxw[i16 & 1], avv);
+            }
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                float vv[4];
+#pragma unroll
+                for (int j16 = 0; j16 < 4; j16++)
+                    vv[j16] = acc[i16][j16][r] * p.alpha * csv[j16];
+                if (auxp) {
+                    float gx[4], gy[4];
+#pragma unroll
+                    for (int j16 = 0; j16 < 4; j16++)
+                        gx[j16] = bf2f(avv[r][j16]);
+                    gelu_grad_vec<4>(gx, gy);
+#pragma unroll
+                    for (int j16 = 0; j16 < 4; j16++) vv[j16] *= gy[j16];
+                }
+#pragma unroll
+                for (int j16 = 0; j16 < 4; j16++) {
+                    ushort_t cb = f2bf(vv[j16] + bvv[j16]);
+                    colacc[j16] += bf2f(cb);
+                    cbv[r][j16] = cb;
+                }
+            }
+            we.store(Cp + (gi0 + i16 * 16) * ldc + cj, cbv);
+        }
+    } else {
 #pragma unroll
     for (int i16 = 0; i16 < 8; i16++) {
 #pragma unroll
@@ -1702,6 +1984,7 @@ __global__ __launch_bounds__(NT8) void gemm_nt_fast8p_kernel(GemmParams p) {
             }
         }
     }
+    }
     if (colp) {
         // this wave's 128 rows: fold the 4 kq lane groups, one store
 #pragma unroll
@@ -1716,7 +1999,12 @@ __global__ __launch_bounds__(NT8) void gemm_nt_fast8p_kernel(GemmParams p) {
 
 void launch_gemm_nt_fast8p(const GemmParams& p, hipStream_t stream) {
     dim3 grid(p.N / BN8, p.M / BM8, p.nproblems);
-    hipLaunchKernelGGL(gemm_nt_fast8p_kernel, grid, dim3(NT8), 0, stream, p);
+    if (p.wide_epi)
+        hipLaunchKernelGGL(gemm_nt_fast8p_kernel<true>, grid, dim3(NT8), 0,
+                           stream, p);
+    else
+        hipLaunchKernelGGL(gemm_nt_fast8p_kernel<false>, grid, dim3(NT8), 0,
+                           stream, p);
 }
 
 // ------- split-K-only TN variant (32 KiB arena, 4 blocks/CU) -------
@@ -1842,6 +2130,18 @@ void launch_gemm_tn_sk(const GemmParams& p, hipStream_t stream) {
 //    tiles, 2 blocks/CU of the plain 2-buf kernel beats any 1-block/CU
 //    in-ring overlap. The wide-tile nt5p wins come from intensity AND
 //    persistence together, not persistence alone
+//  - 16-byte register-epilogue STORES (WideEpi) where they did not pay
+//    (scripts/wide_epi_ab.py, 10 interleaved rounds, TF median [min,max]):
+//    nt5p EPI_GELU_PAIR 473.2 [409.5,478.5] -> 474.5 [459.6,477.5] (a
+//    second session 477.4 -> 469.5), nt5p plain C 627.6 [622.9,630.0] ->
+//    617.2 [609.8,618.4]; nt8p down-proj 792.4 -> 792.1, nt8p square
+//    833.6 -> 835.1. 8x fewer store instructions bought nothing on these,
+//    so the K=512 tail is not store-issue-bound; the code stays
+//    selectable (set_wide_epilogue_mode(2), set_wide_epilogue_nt8p) and
+//    off. What did pay: dH 390.3 -> 456.6 with early 16-byte aux loads
+//    AND wide stores (442.6 with the loads alone), EPI_GELU 529.2 -> 542.8
+//  - nt8p for the K=512 dH with the same wide aux path: 355.6 -> 461.1 TF,
+//    level with nt5p's 463.4, not ahead: GLOM_NT8P_MINK stays 2048
 // The shipping set: gemm_nt_fast (128^2 glds 2-buf), gemm_nt_fast3/4
 // (128x256 8-wave, 2-buf / 3-ring), gemm_nt_fast5p (persistent
 // continuous-ring, default for M%512==0 plain/GELUGRAD epilogues),

@@ -164,15 +164,30 @@ __global__ __launch_bounds__(NT256) void k_colsum_part(
 }
 
 // stage 2: out[p][c] = bf16(sum_rc partials[p][rc][c])
-__global__ __launch_bounds__(NT256) void k_colsum_fin(
+// Each column is one f32 chain added in rc order (that order fixes the
+// dB1/dB2 bits), so the only parallelism is across columns and in the
+// memory system: one-wave blocks spread the columns over 4x as many CUs
+// as 256-thread blocks would, and the row loop issues CSF_UNROLL
+// independent loads before the in-order adds consume them.
+#define CSF_NT 64
+#define CSF_UNROLL 16
+__global__ __launch_bounds__(CSF_NT) void k_colsum_fin(
         const float* __restrict__ partials, ushort_t* __restrict__ out,
         long C, int RB) {
-    int c = blockIdx.x * NT256 + threadIdx.x;
+    long c = (long)blockIdx.x * CSF_NT + threadIdx.x;
     int p = blockIdx.y;
     if (c >= C) return;
     const float* base = partials + (long)p * RB * C + c;
     float acc = 0.f;
-    for (int rc = 0; rc < RB; rc++) acc += base[(long)rc * C];
+    int rc = 0;
+    for (; rc + CSF_UNROLL <= RB; rc += CSF_UNROLL) {
+        float v[CSF_UNROLL];
+#pragma unroll
+        for (int u = 0; u < CSF_UNROLL; u++) v[u] = base[(long)(rc + u) * C];
+#pragma unroll
+        for (int u = 0; u < CSF_UNROLL; u++) acc += v[u];
+    }
+    for (; rc < RB; rc++) acc += base[(long)rc * C];
     out[(long)p * C + c] = f2bf(acc);
 }
 
@@ -183,16 +198,16 @@ void launch_colsum(const void* in, float* partials, void* out, int nprob,
     hipLaunchKernelGGL(k_colsum_part,
                        dim3(ctiles, RB, nprob), dim3(NT256), 0, s,
                        (const ushort_t*)in, partials, M, C, RB);
-    hipLaunchKernelGGL(k_colsum_fin, dim3(cdivl(C, NT256), nprob),
-                       dim3(NT256), 0, s, partials, (ushort_t*)out, C, RB);
+    hipLaunchKernelGGL(k_colsum_fin, dim3(cdivl(C, CSF_NT), nprob),
+                       dim3(CSF_NT), 0, s, partials, (ushort_t*)out, C, RB);
 }
 
 // stage 2 alone, for partials a GEMM epilogue already wrote
 // (GemmParams::colsum_out): out[p][c] = bf16(sum_rb partials[p][rb][c])
 void launch_colsum_fin(const float* partials, void* out, int nprob, long C,
                        int RB, hipStream_t s) {
-    hipLaunchKernelGGL(k_colsum_fin, dim3(cdivl(C, NT256), nprob),
-                       dim3(NT256), 0, s, partials, (ushort_t*)out, C, RB);
+    hipLaunchKernelGGL(k_colsum_fin, dim3(cdivl(C, CSF_NT), nprob),
+                       dim3(CSF_NT), 0, s, partials, (ushort_t*)out, C, RB);
 }
 
 // --------------------------------------------------------------------- //

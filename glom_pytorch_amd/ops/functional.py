@@ -179,34 +179,42 @@ class GlomStepFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, tokens, levels, pos, bw1, bb1, bw2, bb2,
                 tw1, tb1, tw2, tb2, attend_self, mask,
-                bw1t, bw2t, tw1t, tw2t, slab_ref=None):
+                bw1t, bw2t, tw1t, tw2t, slab_ref=None,
+                save_for_bwd=True):
         # slab_ref: optional (slab, idx) — write the step output straight
         # into the preallocated trajectory slab (untracked alias return)
+        # save_for_bwd: False on forward-only steps (decided by glom_step,
+        # outside this Function) — the FF pre-activations, which only the
+        # backward reads, are then neither allocated nor written
         ext = _load_extension()
         slab, sidx = slab_ref if slab_ref is not None else (None, 0)
         if (torch.is_grad_enabled()
                 and os.environ.get("GLOM_FWD_STREAMS", "0") != "1"):
+            # never taken: grad mode is always disabled inside a custom
+            # Function.forward, so GLOM_FWD_STREAMS has no effect and
+            # training and inference both run the fork below
             (out, bhp, bha, thp, tha, probs, rnorm,
              tdin) = ext.glom_step_fwd(
                 tokens, levels, pos, bw1, bb1, bw2, bb2, tw1, tb1, tw2,
-                tb2, attend_self, mask, slab, sidx)
+                tb2, attend_self, mask, slab, sidx, save_for_bwd)
         else:
-            # inference: the three per-iteration chains (bottom-up MLP,
-            # top-down MLP, consensus attention) only depend on `levels`;
-            # forking them onto side streams overlaps their tail waves
-            # (+10% forward throughput). Training keeps one stream: the
-            # backward-dominated step measured no gain from the fork.
+            # the three per-iteration chains (bottom-up MLP, top-down MLP,
+            # consensus attention) only depend on `levels`; forking them
+            # onto side streams overlaps their tail waves (+10% forward
+            # throughput measured on inference).
             cur = torch.cuda.current_stream()
             s_td, s_at, _ = GlomStepFn._side_streams()
             ev = torch.cuda.Event()
             ev.record(cur)
             buY, bhp, bha, _ = ext.grouped_ff_fwd(tokens, levels, None,
-                                                  bw1, bb1, bw2, bb2, 0)
+                                                  bw1, bb1, bw2, bb2, 0,
+                                                  save_for_bwd)
             with torch.cuda.stream(s_td):
                 s_td.wait_event(ev)
                 tdY, thp, tha, tdin = ext.grouped_ff_fwd(None, levels, pos,
                                                          tw1, tb1, tw2,
-                                                         tb2, 1)
+                                                         tb2, 1,
+                                                         save_for_bwd)
             with torch.cuda.stream(s_at):
                 s_at.wait_event(ev)
                 cons, probs, rnorm = ext.consensus_fwd(levels, attend_self,
@@ -216,7 +224,8 @@ class GlomStepFn(torch.autograd.Function):
             # boundary tensors crossing back to the main stream: pin their
             # blocks until the main stream catches up (allocator safety)
             for t in (tdY, thp, tha, tdin, cons, probs, rnorm):
-                t.record_stream(cur)
+                if t.numel():
+                    t.record_stream(cur)
             out = ext.level_mix_fwd(levels, buY, tdY, cons, slab, sidx)
         ctx.save_for_backward(tokens, levels, pos, bw1, bw2, tw1, tw2,
                               bhp, bha, thp, tha, probs, rnorm, mask,
@@ -238,7 +247,7 @@ class GlomStepFn(torch.autograd.Function):
                 bw1t, bw2t, tw1t, tw2t, tdin)
             return (dTokens, dLevels, dPos, dbw1, dbb1, dbw2, dbb2,
                     dtw1, dtb1, dtw2, dtb2, None, None, None, None, None,
-                    None, None)
+                    None, None, None)
         if os.environ.get("GLOM_BWD_FORK", "3") == "3":
             cur = torch.cuda.current_stream()
             s_td, s_at, _ = GlomStepFn._side_streams()
@@ -267,7 +276,7 @@ class GlomStepFn(torch.autograd.Function):
             dPos = ext.dpos(td[1])
             return (bu[0], dLevels, dPos, bu[2], bu[3], bu[4], bu[5],
                     td[2], td[3], td[4], td[5], None, None, None, None,
-                    None, None, None)
+                    None, None, None, None)
         # 4-way fork variant (weight grads on a dedicated stream): measured
         # slightly SLOWER than the 3-way fork above (sync overhead), kept
         # behind GLOM_BWD_FORK=4 for future tuning.
@@ -314,7 +323,7 @@ class GlomStepFn(torch.autograd.Function):
         dPos = ext.dpos(td_dl)
         return (bu_dt, dLevels, dPos, bu_w1, bu_db1, bu_w2, bu_b2,
                 td_w1, td_db1, td_w2, td_b2, None, None, None, None, None,
-                None, None)
+                None, None, None)
 
 
 def _transposed_weights(model):
@@ -335,16 +344,33 @@ def _transposed_weights(model):
         )
 
 
+# Test / A-B hook: True keeps the FF pre-activations on every step, as
+# before forward-only steps learned to skip them (GLOM_SAVE_HPRE=1).
+FORCE_SAVE_FOR_BWD = os.environ.get("GLOM_SAVE_HPRE", "0") == "1"
+
+
+def _needs_bwd(*tensors):
+    """Will autograd record a backward through a step on these inputs?
+    Must be asked OUTSIDE Function.forward (grad mode is off in there)."""
+    if FORCE_SAVE_FOR_BWD:
+        return True
+    return torch.is_grad_enabled() and any(
+        t is not None and t.requires_grad for t in tensors)
+
+
 def glom_step(model, tokens, levels, pos, mask, wts=None, slab_ref=None):
     bw = model.bottom_up.net
     tw = model.top_down.net
     if wts is None:
         wts = (None, None, None, None)
+    args = (tokens, levels, pos,
+            bw[1].weight[..., 0], bw[1].bias, bw[3].weight[..., 0],
+            bw[3].bias,
+            tw[1].weight[..., 0], tw[1].bias, tw[3].weight[..., 0],
+            tw[3].bias)
     return GlomStepFn.apply(
-        tokens, levels, pos,
-        bw[1].weight[..., 0], bw[1].bias, bw[3].weight[..., 0], bw[3].bias,
-        tw[1].weight[..., 0], tw[1].bias, tw[3].weight[..., 0], tw[3].bias,
-        model.attention.attend_self, mask, *wts, slab_ref)
+        *args, model.attention.attend_self, mask, *wts, slab_ref,
+        _needs_bwd(*args))
 
 
 _TAIL_STREAM = None
@@ -443,7 +469,8 @@ def glom_forward(model, img, iters, levels=None, return_all=False,
                         bw[3].weight[..., 0], bw[3].bias,
                         tw[1].weight[..., 0], tw[1].bias,
                         tw[3].weight[..., 0], tw[3].bias,
-                        model.attention.attend_self, mask, slab, t + 1)
+                        model.attention.attend_self, mask, slab, t + 1,
+                        FORCE_SAVE_FOR_BWD)
                     levels = out8[0]
                     if return_all:
                         steps.append(levels)
