@@ -56,6 +56,52 @@ int g_nt8p_mode = []() {
 
 void set_nt8p(bool on) { g_nt8p_mode = on ? 1 : 0; }
 
+// TN kernel with direct-to-LDS staging and transposed LDS reads
+// (gemm_tn_tr): bit-identical to gemm_tn_fast / gemm_tn_sk, so this is a
+// pure speed switch.
+//   0 = never (GLOM_TN_TR=0): the repack kernels, as before
+//   1 = where it measured faster (default; tn_tr_auto below)
+//   2 = every eligible TN call
+// set_tn_tr(bool) picks 2 / 0 and set_tn_tr_mode(int) any of them, for
+// within-process A/B (scripts/tn_tr_ab.py) and the tests. The variant is
+// the split-K pipeline point (1: BK 64 x 2 buffers, 2: BK 32 x 3-ring,
+// 3: BK 32 x 2 buffers; GLOM_TN_TR_VARIANT / set_tn_tr_variant).
+int g_tn_tr = []() {
+    const char* e = getenv("GLOM_TN_TR");
+    return (e && e[0] >= '0' && e[0] <= '2') ? e[0] - '0' : 1;
+}();
+int g_tn_tr_variant = []() {
+    const char* e = getenv("GLOM_TN_TR_VARIANT");
+    return (e && e[0] >= '1' && e[0] <= '3') ? e[0] - '0' : 1;
+}();
+void set_tn_tr(bool on) { g_tn_tr = on ? 2 : 0; }
+void set_tn_tr_mode(int64_t m) {
+    TORCH_CHECK(m >= 0 && m <= 2, "tn_tr mode is 0..2");
+    g_tn_tr = (int)m;
+}
+int64_t get_tn_tr_mode() { return g_tn_tr; }
+void set_tn_tr_variant(int64_t v) {
+    TORCH_CHECK(v >= 1 && v <= 3, "tn_tr variant is 1..3");
+    g_tn_tr_variant = (int)v;
+}
+int64_t get_tn_tr_variant() { return g_tn_tr_variant; }
+// Default policy, from the op-level A/B (profiles/tn_tr_ab.txt): every
+// split-K call and the non-split ones measured at K = 4096 and 8192 win
+// (min above the repack kernels' max); at K = 1024 and the K = 256
+// attention dv / dk-hat the two are level, and with those on the new
+// kernel the headline step measured slower (its 64 KiB arena against
+// tn_fast's 34 KiB), so short-K non-split calls keep gemm_tn_fast
+static bool tn_tr_auto(const GemmParams& p) {
+    return p.splitk > 1 || p.K >= 4096;
+}
+// Re-blocked split-K finish (gemm_finish4, 16-byte slab loads): same bits
+// as the scalar kernel. GLOM_FINISH_WIDE=0 / set_finish_wide(false) revert.
+int g_finish_wide = []() {
+    const char* e = getenv("GLOM_FINISH_WIDE");
+    return (e && e[0] == '0') ? 0 : 1;
+}();
+void set_finish_wide(bool on) { g_finish_wide = on ? 1 : 0; }
+
 // GELU placement: 0 = standalone bandwidth pass after the up-projection
 // (round-1 measurement); 1 = EPI_GELU_PAIR fused into the up-projection
 // epilogue (nt5p register epilogue writes both Hpre and gelu(Hpre),
@@ -236,15 +282,30 @@ void run_gemm(GemmParams& p, hipStream_t s, const torch::TensorOptions& opts,
                       && (p.epilogue == EPI_NONE
                           || p.epilogue == EPI_GELUGRAD)
                       && (long)(p.N / 256) * (p.M / 256) * p.nproblems >= 256;
+    // whole K-steps only: K % 64 == 0 makes every split-K slice (`per` is
+    // a multiple of 64) a whole number of stages; K % 8 tails stay on the
+    // repack kernels. 16-byte DMA sources need 16-byte-aligned bases.
+    auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
+    bool tn_al = al16(p.A.base) && al16(p.B.base);
+    if (p.A.flags & OP_TABLE)
+        for (int g = 0; g < p.nproblems; g++) tn_al = tn_al && al16(p.Atab[g]);
+    if (p.B.flags & OP_TABLE)
+        for (int g = 0; g < p.nproblems; g++) tn_al = tn_al && al16(p.Btab[g]);
+    const bool tn_tr = (g_tn_tr == 2 || (g_tn_tr == 1 && tn_tr_auto(p)))
+                       && tn_fast && p.K % 64 == 0 && p.K >= 64
+                       && tn_al && p.A.sin % 8 == 0 && p.A.sout % 8 == 0
+                       && p.B.sin % 8 == 0 && p.B.sout % 8 == 0;
     p.wide_epi = !wide_epi_ok(p) ? 0
                  : nt8p ? g_wide_epi_nt8p : nt5p_wide_bits(p.epilogue);
     if (disp_dbg)
         fprintf(stderr,
                 "[dispatch] L%d M%ld N%ld K%ld epi%d nt3=%d nt5p=%d on=%d "
-                "nt8p=%d ctabflag=%d m512=%d\n",
+                "nt8p=%d ctabflag=%d m512=%d tn_tr=%d sk=%d finw=%d\n",
                 p.layout, (long)p.M, (long)p.N, (long)p.K, p.epilogue,
                 (int)nt3, (int)nt5p, (int)nt5p_on, (int)nt8p,
-                (int)(p.Cflags & OP_TABLE), (int)(p.M % 512 == 0));
+                (int)(p.Cflags & OP_TABLE), (int)(p.M % 512 == 0),
+                tn_tr ? (p.splitk > 1 ? g_tn_tr_variant : 1) : 0,
+                p.splitk, g_finish_wide);
     if (nt8p)
         launch_gemm_nt_fast8p(p, s);
     else if (nt5p)
@@ -253,6 +314,8 @@ void run_gemm(GemmParams& p, hipStream_t s, const torch::TensorOptions& opts,
         launch_gemm_nt_fast4(p, s);   // 3-ring counted-vmcnt variant
     else if (nt_fast)
         launch_gemm_nt_fast(p, s);
+    else if (tn_tr)
+        launch_gemm_tn_tr(p, g_tn_tr_variant, s);
     else if (tn_fast && p.splitk > 1)
         launch_gemm_tn_sk(p, s);     // 32KB arena: 4 blocks/CU for the
     else if (tn_fast)                // weight-grad split-K launches
@@ -263,7 +326,7 @@ void run_gemm(GemmParams& p, hipStream_t s, const torch::TensorOptions& opts,
         launch_gemm(p, s);
     check_launch();
     if (p.splitk > 1) {
-        launch_gemm_finish(p, s);
+        launch_gemm_finish(p, s, g_finish_wide == 1);
         check_launch();
     }
 }
@@ -880,6 +943,25 @@ double bench_gemm(int64_t M, int64_t N, int64_t K, int64_t layout,
     return ms / reps;
 }
 
+// Test-and-tuning-only: C[g] = A[g]^T B[g] for A (G,K,M), B (G,K,N) through
+// run_gemm's TN dispatch (EPI_NONE), so a TN result for a chosen shape can
+// be taken out of the extension.
+torch::Tensor gemm_tn(torch::Tensor A, torch::Tensor B) {
+    CHECK_IN(A); CHECK_IN(B);
+    TORCH_CHECK(A.dim() == 3 && B.dim() == 3 && A.size(0) == B.size(0)
+                && A.size(1) == B.size(1), "A (G,K,M), B (G,K,N)");
+    const int64_t G = A.size(0), K = A.size(1), M = A.size(2),
+                  N = B.size(2);
+    TORCH_CHECK(M % 8 == 0 && N % 8 == 0, "M and N must be /8");
+    auto C = torch::empty({G, M, N}, A.options());
+    GemmParams p = base_params(M, N, K, LAYOUT_TN, G, G, 1.0f);
+    p.A.base = A.data_ptr(); p.A.sin = K * M; p.A.ld = M;
+    p.B.base = B.data_ptr(); p.B.sin = K * N; p.B.ld = N;
+    p.Cbase = C.data_ptr(); p.Csin = M * N; p.Cld = N;
+    run_gemm(p, cur_stream(), A.options(), true);
+    return C;
+}
+
 void add4_into(torch::Tensor a, torch::Tensor b, torch::Tensor c,
                torch::Tensor d, torch::Tensor out) {
     CHECK_IN(a); CHECK_IN(b); CHECK_IN(c); CHECK_IN(d); CHECK_IN(out);
@@ -1369,6 +1451,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("Hact"), py::arg("mode"),
           py::arg("td_in") = c10::nullopt);
     m.def("set_nt8p", &set_nt8p, "toggle the 8-phase NT kernel (A/B)");
+    m.def("set_tn_tr", &set_tn_tr,
+          "toggle the transposed-read TN kernel (A/B, same bits)");
+    m.def("set_tn_tr_mode", &set_tn_tr_mode,
+          "0 never, 1 default policy, 2 every eligible TN call");
+    m.def("get_tn_tr_mode", &get_tn_tr_mode);
+    m.def("get_tn_tr_variant", &get_tn_tr_variant);
+    m.def("set_tn_tr_variant", &set_tn_tr_variant,
+          "split-K pipeline point of the transposed-read TN kernel (1..3)");
+    m.def("set_finish_wide", &set_finish_wide,
+          "toggle the re-blocked split-K finish (A/B, same bits)");
+    m.def("gemm_tn", &gemm_tn, "C = A^T B per group (tests / tuning only)");
     m.def("set_wide_epilogue", &set_wide_epilogue,
           "toggle the 16-byte register epilogue of nt5p (A/B)");
     m.def("set_wide_epilogue_mode", &set_wide_epilogue_mode,

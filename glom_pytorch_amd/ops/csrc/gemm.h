@@ -88,7 +88,9 @@ struct GemmParams {
 };
 
 void launch_gemm(const GemmParams& p, hipStream_t stream);
-void launch_gemm_finish(const GemmParams& p, hipStream_t stream);
+// wide: re-blocked 16-byte kernel where C allows it (same bits)
+void launch_gemm_finish(const GemmParams& p, hipStream_t stream,
+                        bool wide = true);
 void launch_gemm_nt_fast(const GemmParams& p, hipStream_t stream);
 void launch_gemm_tn_fast(const GemmParams& p, hipStream_t stream);
 void launch_gemm_nn_fast(const GemmParams& p, hipStream_t stream);
@@ -97,3 +99,5 @@ void launch_gemm_nt_fast4(const GemmParams& p, hipStream_t stream);
 void launch_gemm_nt_fast5p(const GemmParams& p, hipStream_t stream);
 void launch_gemm_nt_fast8p(const GemmParams& p, hipStream_t stream);
 void launch_gemm_tn_sk(const GemmParams& p, hipStream_t stream);
+// direct-to-LDS + transposed-read TN kernel; variant: see gemm_fast.hip
+void launch_gemm_tn_tr(const GemmParams& p, int variant, hipStream_t stream);

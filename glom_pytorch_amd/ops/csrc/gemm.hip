@@ -249,7 +249,59 @@ void launch_gemm(const GemmParams& p, hipStream_t stream) {
     hipLaunchKernelGGL(gemm_kernel, grid, dim3(NTHREADS), 0, stream, p);
 }
 
-void launch_gemm_finish(const GemmParams& p, hipStream_t stream) {
+// Re-blocked finish for strided (non-table) C with N % 4 == 0: one thread
+// sums 4 consecutive columns, 16-byte slab loads issued in batches of up to
+// 8 slices before the first add, one 8-byte bf16 store. Per element the
+// adds run in the same order (s = 0; s += slice 0 .. splitk-1) and the
+// rounding is the same as in gemm_finish_kernel: identical bits.
+// grid: (ceil(M*N/4 / 256), nproblems).
+__global__ __launch_bounds__(NTHREADS) void gemm_finish4_kernel(GemmParams p) {
+    const long mn = (long)p.M * p.N;
+    const long e0 = ((long)blockIdx.x * NTHREADS + threadIdx.x) * 4;
+    if (e0 >= mn) return;
+    const int pid = blockIdx.y;
+    const long slab = (long)p.nproblems * mn;      // slice stride
+    const float* w = p.ws + (long)pid * mn + e0;
+    float s[4] = {0.f, 0.f, 0.f, 0.f};
+    for (int sl0 = 0; sl0 < p.splitk; sl0 += 8) {
+        f32x4 v[8];
+#pragma unroll
+        for (int u = 0; u < 8; u++)
+            if (sl0 + u < p.splitk)
+                v[u] = *(const f32x4*)(w + (long)(sl0 + u) * slab);
+#pragma unroll
+        for (int u = 0; u < 8; u++)
+            if (sl0 + u < p.splitk) {
+#pragma unroll
+                for (int e = 0; e < 4; e++) s[e] += v[u][e];
+            }
+    }
+    ushort_t* Cp = (ushort_t*)p.Cbase + (long)(pid % p.nInner) * p.Csin
+                   + (long)(pid / p.nInner) * p.Csout;
+    const long i = e0 / p.N, j = e0 % p.N;
+    union { unsigned long long q; ushort_t u[4]; } o;
+#pragma unroll
+    for (int e = 0; e < 4; e++) o.u[e] = f2bf(s[e] * p.alpha);
+    *(unsigned long long*)(Cp + i * p.Cld + j) = o.q;
+}
+
+// the 16-byte slab loads / 8-byte store need a strided C whose rows,
+// problem strides and base keep 4-element groups aligned
+static bool finish4_ok(const GemmParams& p) {
+    return !(p.Cflags & OP_TABLE) && p.N % 4 == 0 && p.Cld % 4 == 0
+           && p.Csin % 4 == 0 && p.Csout % 4 == 0
+           && ((uintptr_t)p.Cbase & 7) == 0 && ((uintptr_t)p.ws & 15) == 0;
+}
+
+void launch_gemm_finish(const GemmParams& p, hipStream_t stream, bool wide) {
+    if (wide && finish4_ok(p)) {
+        long quads = (long)p.M * p.N / 4;
+        hipLaunchKernelGGL(gemm_finish4_kernel,
+                           dim3((quads + NTHREADS - 1) / NTHREADS,
+                                p.nproblems),
+                           dim3(NTHREADS), 0, stream, p);
+        return;
+    }
     long total = (long)p.nproblems * p.M * p.N;
     hipLaunchKernelGGL(gemm_finish_kernel,
                        dim3((total + NTHREADS - 1) / NTHREADS),

@@ -13,6 +13,10 @@
 // and writes 8 x ds_write_b128 into the swizzled [out-dim][k] image —
 // replacing the v1 per-element LDS scatter (8x fewer, 8x wider writes).
 //
+// gemm_tn_tr: the same TN tiles copied as stored by global_load_lds and
+// transposed by ds_read_b64_tr_b16 on the way into the MFMA (K % 64 == 0;
+// default for the split-K weight grads). See the comment above it.
+//
 // Preconditions (host-checked, fast_ok): M%128==0, N%128==0, K%64==0
 // (TN: K%8==0 with row predicates), all row strides %8==0, no on-load
 // transforms. Everything else falls back to the generic gemm_kernel.
@@ -2110,6 +2114,296 @@ void launch_gemm_tn_sk(const GemmParams& p, hipStream_t stream) {
     hipLaunchKernelGGL(gemm_tn_sk_kernel, grid, dim3(NTHREADS), 0, stream, p);
 }
 
+// ---------------------------------------------------------------- //
+// TN kernel with direct-to-LDS staging and transposed LDS reads.
+//
+// Both TN operands are stored [k][out-dim]. The tiles are copied AS STORED
+// ([BK k-rows][128 out-dim columns], 256-byte rows) by global_load_lds
+// width 16 — no VGPR round trip, no register repack — and the transpose
+// the MFMA needs (8 consecutive k per lane) happens in the LDS read path:
+// ds_read_b64_tr_b16 hands lane i of a 16-lane group column i of a
+// 4-row x 16-column block, so two of them (rows kq*8+0..3, kq*8+4..7) give
+// exactly the short8 the repack kernels read with one ds_read_b128. Same
+// MFMA, same k -> lane-group map, ascending k: results are bit-identical
+// to gemm_tn_fast / gemm_tn_sk.
+//
+// LDS image (guide T10 layout (b)): 16-byte chunk ch of row r sits at
+// byte 256*r + 16*(ch ^ tr_swz(r)), tr_swz(r) = ((r&3)<<2) | ((r>>2)&3).
+// The DMA destination is linear, so the XOR goes on the per-lane SOURCE
+// chunk (as in stage_glds). Bank check (bank = (addr/4) % 64, conflicts
+// count per 32-lane half, 8 bytes = 2 banks per lane): a 256-byte row is
+// exactly 64 banks, so the bank pair of a lane is 2*pos + (p&1) with
+// pos = (c0 + (p>>1)) ^ tr_swz(row). A half holds lane groups kq and kq+1,
+// i.e. rows r0+q and r0+8+q (q = 0..3) of one 16-column block: q toggles
+// pos bits 2-3, p>>1 bit 0, the +8 rows bit 1 -> 16 distinct chunks x 2
+// halves of a chunk = 32 distinct bank pairs, conflict-free.
+
+typedef short short4v __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ int tr_swz(int row) {
+    return ((row & 3) << 2) | ((row >> 2) & 3);
+}
+
+// This wave's share of one [BK][128] operand tile: BK/4 DMA chunks of
+// 4 rows (1 KB), BK/16 per wave. Lane l of a chunk lands at linear byte
+// 16*l, i.e. row l>>4, chunk position l&15, and fetches the source chunk
+// that the image keeps at that position.
+template <int BK>
+__device__ __forceinline__ void stage_glds_km(
+        ushort_t* lds, const ushort_t* src, long ld, int k0, int c0,
+        int wid, int lane) {
+#pragma unroll
+    for (int c = 0; c < BK / 16; c++) {
+        int chunk = wid * (BK / 16) + c;
+        int row = chunk * 4 + (lane >> 4);
+        int ch = (lane & 15) ^ tr_swz(row);
+        const ushort_t* gaddr = src + (long)(k0 + row) * ld + c0 + ch * 8;
+        ushort_t* laddr = lds + chunk * 512;  // wave-uniform chunk base
+        __builtin_amdgcn_global_load_lds(
+            (const __attribute__((address_space(1))) unsigned int*)gaddr,
+            (__attribute__((address_space(3))) unsigned int*)laddr, 16, 0, 0);
+    }
+}
+
+// Byte offset, inside a [BK][128] image, of this lane's address for the
+// transposed read of rows r0+q (r0 % 4 == 0, q = 0..3) x columns
+// [col0, col0+16): lane 4q+p of each 16-lane group addresses row q,
+// columns 4p..4p+3 of the block.
+__device__ __forceinline__ unsigned tr_off(int r0, int col0, int lane) {
+    const int q = (lane >> 2) & 3, p = lane & 3;
+    const int ch = (col0 >> 3) + (p >> 1);
+    const int r = r0 + q;
+    return (unsigned)(r * 256 + ((ch ^ tr_swz(r)) << 4) + ((p & 1) << 3));
+}
+
+// The transposed read is inline asm: through the builtin hipcc cannot
+// tell the read from the in-flight global_load_lds destinations and puts
+// s_waitcnt vmcnt(0) in front of the first read of every k-step, which
+// drains the prefetch. The compiler therefore does NOT count these reads
+// in lgkmcnt: every consumer sits behind tr_wait<N>() + tr_pin().
+// Needs EXEC all ones: wave-uniform control flow only.
+template <int OFF>
+__device__ __forceinline__ short4v tr_read(unsigned addr) {
+    short4v v;
+    asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2"
+                 : "=v"(v) : "v"(addr), "n"(OFF) : "memory");
+    return v;
+}
+template <int N>
+__device__ __forceinline__ void tr_wait() {
+    asm volatile("s_waitcnt lgkmcnt(%0)" :: "n"(N) : "memory");
+}
+// makes every later use of `v` depend on a point after the wait
+__device__ __forceinline__ void tr_pin(short4v& v) {
+    asm volatile("" : "+v"(v));
+}
+
+// the 8 reads of one operand's four fragments for one MFMA k-group
+template <int OFF>
+__device__ __forceinline__ void tr_read4(
+        short4v (&f)[4][2], const unsigned (&off)[4][2], unsigned sb) {
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+        f[i][0] = tr_read<OFF>(off[i][0] + sb);
+        f[i][1] = tr_read<OFF>(off[i][1] + sb);
+    }
+}
+__device__ __forceinline__ void tr_pin4(short4v (&f)[4][2]) {
+#pragma unroll
+    for (int i = 0; i < 4; i++) { tr_pin(f[i][0]); tr_pin(f[i][1]); }
+}
+
+// BK: k-rows per stage (64 or 32); NST: stages in the ring (2: the
+// nt_fast loop, one barrier + vmcnt(0) per step; 3: counted vmcnt, the
+// stage after next streams during this step's MFMAs); SPLIT: split-K only
+// (f32 slab epilogue, arena = the ring alone).
+template <int BK, int NST, bool SPLIT>
+__global__ __launch_bounds__(NTHREADS) void gemm_tn_tr_kernel(GemmParams p) {
+    constexpr int OPER = BK * 128;           // elements per operand stage
+    constexpr int STAGE = 2 * OPER;
+    constexpr int RING = NST * STAGE;
+    constexpr int ARENA =
+        (SPLIT || RING >= 128 * EPI_LDS_ROW) ? RING : 128 * EPI_LDS_ROW;
+    constexpr int NL = 2 * (BK / 16);        // DMA loads per wave per stage
+    static_assert(NST == 2 || NST == 3, "ring depth");
+    static_assert(NL == 4 || NL == 8, "vmcnt immediates below");
+    __shared__ ushort_t smem[ARENA];         // ONE arena (see nt_fast)
+
+    int pid = blockIdx.z;
+    int slice = 0, k_begin = 0, k_end = p.K;
+    if (p.splitk > 1) {
+        pid = blockIdx.z % p.nproblems;
+        slice = blockIdx.z / p.nproblems;
+        int per = ((p.K + FBK - 1) / FBK + p.splitk - 1) / p.splitk * FBK;
+        k_begin = slice * per;
+        k_end = min(p.K, k_begin + per);
+    }
+    int nwg = gridDim.x * gridDim.y;
+    int bid = blockIdx.y * gridDim.x + blockIdx.x;
+    {
+        int q = nwg >> 3, r = nwg & 7, xcd = bid & 7, off = bid >> 3;
+        bid = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + off;
+    }
+    const int n0 = (bid / gridDim.y) * BN;   // column-major: n outer
+    const int m0 = (bid % gridDim.y) * BM;
+
+    const ushort_t* Ap;
+    const ushort_t* Bp;
+    long lda, ldb;
+    resolve_ptr2(p.A, p.Atab, p.Atabld, pid, p.nInner, &Ap, &lda);
+    resolve_ptr2(p.B, p.Btab, p.Btabld, pid, p.nInner, &Bp, &ldb);
+
+    const int wid = threadIdx.x / WAVE;
+    const int lane = threadIdx.x % WAVE;
+    const int wm = (wid >> 1) * 64;
+    const int wn = (wid & 1) * 64;
+    const int lrow = lane & 15;
+    const int kq = lane >> 4;
+
+    f32x4 acc[4][4] = {};
+
+    // K % 64 == 0 (host-checked) and `per` a multiple of 64: every slice
+    // is a whole number of stages; an empty slice (k_begin >= k_end) runs
+    // no stage at all and stores its zero accumulators
+    const int nk = k_end > k_begin ? (k_end - k_begin) / BK : 0;
+
+    auto stage = [&](int buf, int kt) {
+        ushort_t* Al = smem + buf * STAGE;
+        stage_glds_km<BK>(Al, Ap, lda, k_begin + kt * BK, m0, wid, lane);
+        stage_glds_km<BK>(Al + OPER, Bp, ldb, k_begin + kt * BK, n0, wid,
+                          lane);
+    };
+
+    if (nk > 0) {
+        stage(0, 0);
+        if (NST == 3 && nk > 1) {
+            stage(1, 1);
+            if (NL == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+            else         asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+        } else {
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        }
+        __builtin_amdgcn_s_barrier();
+    }
+
+    // per-lane LDS byte addresses of the fragment reads in stage 0:
+    // [i][h] = rows kq*8 + 4h .. +3 of the 16 columns of fragment i; the
+    // second MFMA k-group of a BK=64 stage is 32 rows = 8192 bytes on
+    // (tr_swz is unchanged by +32 rows), the B tile OPER*2 bytes on
+    const unsigned lds0 = (unsigned)(unsigned long)
+        (__attribute__((address_space(3))) ushort_t*)smem;
+    unsigned aoff[4][2], boff[4][2];
+#pragma unroll
+    for (int i = 0; i < 4; i++)
+#pragma unroll
+        for (int h = 0; h < 2; h++) {
+            aoff[i][h] = lds0 + tr_off(kq * 8 + 4 * h, wm + i * 16, lane);
+            boff[i][h] = lds0 + tr_off(kq * 8 + 4 * h, wn + i * 16, lane);
+        }
+    auto cat = [](short4v lo, short4v hi) -> short8 {
+        return __builtin_shufflevector(lo, hi, 0, 1, 2, 3, 4, 5, 6, 7);
+    };
+
+    for (int kt = 0; kt < nk; kt++) {
+        if (kt + NST - 1 < nk) stage((kt + NST - 1) % NST, kt + NST - 1);
+        const unsigned sb = (unsigned)((kt % NST) * STAGE * 2);
+        short4v a0[4][2], b0[4][2];
+        tr_read4<0>(a0, aoff, sb);
+        tr_read4<OPER * 2>(b0, boff, sb);
+        if constexpr (BK == 64) {
+            // second k-group: A issued before the first group is waited
+            // for, B right after, both in flight under the first MFMAs
+            short4v a1[4][2], b1[4][2];
+            tr_read4<8192>(a1, aoff, sb);
+            tr_wait<8>();
+            tr_pin4(a0); tr_pin4(b0);
+            tr_read4<OPER * 2 + 8192>(b1, boff, sb);
+#pragma unroll
+            for (int i = 0; i < 4; i++)
+#pragma unroll
+                for (int j = 0; j < 4; j++)
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                        cat(a0[i][0], a0[i][1]), cat(b0[j][0], b0[j][1]),
+                        acc[i][j], 0, 0, 0);
+            tr_wait<0>();
+            tr_pin4(a1); tr_pin4(b1);
+#pragma unroll
+            for (int i = 0; i < 4; i++)
+#pragma unroll
+                for (int j = 0; j < 4; j++)
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                        cat(a1[i][0], a1[i][1]), cat(b1[j][0], b1[j][1]),
+                        acc[i][j], 0, 0, 0);
+        } else {
+            tr_wait<0>();
+            tr_pin4(a0); tr_pin4(b0);
+#pragma unroll
+            for (int i = 0; i < 4; i++)
+#pragma unroll
+                for (int j = 0; j < 4; j++)
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(
+                        cat(a0[i][0], a0[i][1]), cat(b0[j][0], b0[j][1]),
+                        acc[i][j], 0, 0, 0);
+        }
+        if (NST == 2) {
+            // drains the in-flight DMA of the next stage + buffer reuse
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            __syncthreads();
+        } else if (kt + 1 < nk) {
+            // stage kt+1 landed; stage kt+2 (issued above) may still fly:
+            // raw barrier, __syncthreads would drain it with vmcnt(0)
+            if (kt + 2 < nk) {
+                if (NL == 8) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
+                else         asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+            } else {
+                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            }
+            __builtin_amdgcn_s_barrier();
+        }
+    }
+
+    if (SPLIT || p.splitk > 1) {
+        float* ws = p.ws + ((long)slice * p.nproblems + pid) * p.M * p.N;
+#pragma unroll
+        for (int i16 = 0; i16 < 4; i16++)
+#pragma unroll
+            for (int j16 = 0; j16 < 4; j16++) {
+                int j = n0 + wn + j16 * 16 + lrow;
+#pragma unroll
+                for (int r = 0; r < 4; r++) {
+                    int i = m0 + wm + i16 * 16 + kq * 4 + r;
+                    ws[(long)i * p.N + j] = acc[i16][j16][r];
+                }
+            }
+        return;
+    }
+    if constexpr (!SPLIT) {
+        __syncthreads();   // all waves done with the ring before staging C
+        gemm_epilogue_lds(p, pid, m0, n0, wm, wn, lrow, kq, acc, smem);
+    }
+}
+
+// variant: 1 = BK 64 x 2 buffers (64 KiB, 2 blocks/CU), 2 = BK 32 x 3-ring
+// (48 KiB, 3 blocks/CU), 3 = BK 32 x 2 buffers (32 KiB, 4 blocks/CU).
+// Non-split calls need the C staging arena and always take variant 1.
+void launch_gemm_tn_tr(const GemmParams& p, int variant, hipStream_t stream) {
+    int sk = p.splitk > 1 ? p.splitk : 1;
+    dim3 grid(p.N / BN, p.M / BM, p.nproblems * sk);
+    dim3 blk(NTHREADS);
+    if (sk == 1)
+        hipLaunchKernelGGL((gemm_tn_tr_kernel<64, 2, false>), grid, blk, 0,
+                           stream, p);
+    else if (variant == 2)
+        hipLaunchKernelGGL((gemm_tn_tr_kernel<32, 3, true>), grid, blk, 0,
+                           stream, p);
+    else if (variant == 3)
+        hipLaunchKernelGGL((gemm_tn_tr_kernel<32, 2, true>), grid, blk, 0,
+                           stream, p);
+    else
+        hipLaunchKernelGGL((gemm_tn_tr_kernel<64, 2, true>), grid, blk, 0,
+                           stream, p);
+}
+
 
 // ---------------------------------------------------------------- //
 // Measured-and-rejected variants (see git history + profiles/README.md):
@@ -2142,7 +2436,28 @@ void launch_gemm_tn_sk(const GemmParams& p, hipStream_t stream) {
 //    AND wide stores (442.6 with the loads alone), EPI_GELU 529.2 -> 542.8
 //  - nt8p for the K=512 dH with the same wide aux path: 355.6 -> 461.1 TF,
 //    level with nt5p's 463.4, not ahead: GLOM_NT8P_MINK stays 2048
+//  - gemm_tn_tr split-K pipeline points that lost (scripts/tn_tr_ab.py,
+//    TF median [min,max] of GEMM + finish; then the headline step, three
+//    alternating runs, ms). Shipped: BK 64 x 2 buffers (64 KiB, 2
+//    blocks/CU): dW1 626.5 [621.5,633.9], dW2 712.5 [704.4,721.1],
+//    step 40.24 / 40.28 / 40.27 (old kernels 41.15 / 41.15 / 41.38).
+//    BK 32 x 2 buffers (32 KiB, 4 blocks/CU): dW1 633.1 [631.2,634.7],
+//    dW2 721.4 [716.8,725.7] - ahead or level alone, but the step is
+//    40.47 / 40.46 / 40.47. BK 32 3-ring with counted vmcnt (48 KiB, 3
+//    blocks/CU): dW1 604.7 [600.2,607.2], dW2 727.0 [706.7,738.8], step
+//    41.34 / 41.40 / 41.43, slower than the old kernels. dW runs beside
+//    the dH / dX streams; the step decides. Both stay selectable
+//    (GLOM_TN_TR_VARIANT=3 / 2)
+//  - gemm_tn_tr for the K=256 attention dv / dk-hat (non-split, 64 KiB
+//    arena vs tn_fast's 34 KiB): level at op level (269.3 vs 269.5 TF),
+//    step 40.5-40.8 vs 40.47 with them on tn_fast: K < 4096 non-split
+//    calls keep gemm_tn_fast
+//  - ds_read_b64_tr_b16 through the compiler builtin: correct, but hipcc
+//    puts s_waitcnt vmcnt(0) before the first read of every k-step (it
+//    cannot tell the read from the in-flight glds destinations), which
+//    drains the prefetch; hence the inline asm + hand-placed lgkmcnt
 // The shipping set: gemm_nt_fast (128^2 glds 2-buf), gemm_nt_fast3/4
 // (128x256 8-wave, 2-buf / 3-ring), gemm_nt_fast5p (persistent
 // continuous-ring, default for M%512==0 plain/GELUGRAD epilogues),
-// gemm_tn_fast(+_sk), gemm_nn_fast.
+// gemm_tn_tr (glds + transposed reads; weight grads), gemm_tn_fast(+_sk)
+// (K % 8 tails, short-K non-split), gemm_nn_fast.
