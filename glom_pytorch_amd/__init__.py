@@ -19,9 +19,12 @@ from glom_pytorch_amd import islands
 from glom_pytorch_amd.islands import (edge_agreement, labels_from_agreement,
                                       island_labels, island_sizes,
                                       island_count)
+from glom_pytorch_amd import contrast
+from glom_pytorch_amd.contrast import column_contrastive_loss
 
 __version__ = "0.2.0"
 
 __all__ = ["Glom", "GroupedFeedForward", "ConsensusAttention", "islands",
            "edge_agreement", "labels_from_agreement", "island_labels",
-           "island_sizes", "island_count"]
+           "island_sizes", "island_count", "contrast",
+           "column_contrastive_loss"]

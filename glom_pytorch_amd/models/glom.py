@@ -247,6 +247,20 @@ class Glom(nn.Module):
         return island_labels(levels, threshold=threshold, grid=(side, side),
                              connectivity=connectivity)
 
+    def contrastive_loss(self, levels_a: torch.Tensor,
+                         levels_b: torch.Tensor, level: int = -1,
+                         **kw) -> torch.Tensor:
+        """Column-contrastive loss between level ``level`` of two
+        ``(B, N, L, D)`` states, e.g. of two corruptions of the same images
+        (see ``glom_pytorch_amd.contrast.column_contrastive_loss``, which
+        takes ``**kw``); differentiable in both."""
+        from glom_pytorch_amd.contrast import column_contrastive_loss
+        if levels_a.dim() != 4 or levels_a.shape != levels_b.shape:
+            raise ValueError("levels_a and levels_b must both be "
+                             "(B, N, L, D) with equal shapes")
+        return column_contrastive_loss(levels_a[:, :, level],
+                                       levels_b[:, :, level], **kw)
+
     # ------------------------------------------------------------------ #
     # Eager (plain PyTorch) path — the semantic specification. CPU tests
     # compare this against an independent loop-level oracle, and GPU tests

@@ -16,6 +16,7 @@
 #include "aux_kernels.h"
 #include "native_ops.h"
 #include "island_kernels.h"
+#include "contrast_kernels.h"
 
 namespace {
 
@@ -205,6 +206,34 @@ void check_launch() {
     TORCH_CHECK(e == hipSuccess, "HIP launch failed: ", hipGetErrorString(e));
 }
 
+// launches of the column-contrastive epilogues by hosting kernel, for the
+// tests: {gemm_nt_fast, generic}
+int64_t g_nce_launches[2] = {0, 0};
+std::vector<int64_t> nce_launch_counts() {
+    return {g_nce_launches[0], g_nce_launches[1]};
+}
+// A/B switch (scripts/contrast_bench.py): false sends the EPI_NCE_* GEMMs
+// to the generic kernel even where gemm_nt_fast is eligible. Both hosts run
+// the same epilogue code. Measured at M = 16384, D = 512: the fast host is
+// 1.6x faster forward, 1.3x forward+backward (profiles/contrast_bench.txt).
+int g_nce_fast = []() {
+    const char* e = getenv("GLOM_NCE_FAST");
+    return (e && e[0] == '0') ? 0 : 1;
+}();
+void set_nce_fast(bool on) { g_nce_fast = on ? 1 : 0; }
+
+// Epilogue preconditions, checked here or by the callers named:
+//   EPI_NONE / bias / colscale  every kernel
+//   EPI_GELUGRAD, EPI_GELU_PAIR every kernel but nt_fast3; aux / out2 set
+//   EPI_SOFTMAX, EPI_SMBWD      nt_fast4 only, launched directly by the
+//                               consensus ops (N == 256, d % 64 == 0)
+//   EPI_GELU                    nt5p only (ask nt5p_takes_up_proj() first)
+//   EPI_NCE_FWD, EPI_NCE_BWD    NT, one problem, no table / bias / colscale,
+//                               arguments via nce_set(); generic kernel for any shape,
+//                               gemm_nt_fast for full tiles (M, N % 128,
+//                               K % 64, rows % 8 elements, 16-byte bases; BWD
+//                               also C 16-byte aligned with Cld % 8); never
+//                               the 256-wide kernels
 // Central dispatcher: picks the tuned full-tile kernels (glds NT / repack
 // TN) when the host-verified preconditions hold, applies split-K when the
 // natural grid underfills the 256 CUs (the weight-grad TN GEMMs: tiny
@@ -215,9 +244,11 @@ void run_gemm(GemmParams& p, hipStream_t s, const torch::TensorOptions& opts,
               bool lds_ok) {
     const bool no_xform = !(p.A.flags & (OP_GELU | OP_POS))
                           && !(p.B.flags & (OP_GELU | OP_POS));
+    const bool nce_generic = !g_nce_fast && (p.epilogue == EPI_NCE_FWD
+                                             || p.epilogue == EPI_NCE_BWD);
     const bool nt_fast = p.layout == LAYOUT_NT && lds_ok && no_xform
                          && p.M % 128 == 0 && p.N % 128 == 0
-                         && p.K % 64 == 0 && p.K >= 64;
+                         && p.K % 64 == 0 && p.K >= 64 && !nce_generic;
     const bool tn_fast = p.layout == LAYOUT_TN && lds_ok && no_xform
                          && p.M % 128 == 0 && p.N % 128 == 0 && p.K % 8 == 0;
     const bool nn_fast = p.layout == LAYOUT_NN && lds_ok && no_xform
@@ -238,7 +269,26 @@ void run_gemm(GemmParams& p, hipStream_t s, const torch::TensorOptions& opts,
             p.ws = ws.data_ptr<float>();
         }
     }
-    const bool nt3 = nt_fast && p.N % 256 == 0 && p.N >= 1024;
+    const bool nce = p.epilogue == EPI_NCE_FWD || p.epilogue == EPI_NCE_BWD;
+    if (nce) {
+        auto al = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
+        TORCH_CHECK(p.layout == LAYOUT_NT && p.nproblems == 1
+                    && !((p.A.flags | p.B.flags | p.Cflags) & OP_TABLE)
+                    && !p.has_bias && !p.has_colscale,
+                    "EPI_NCE_* needs one plain NT problem");
+        const NceArgs q = nce_get(p);
+        TORCH_CHECK(q.rrow && q.rcol && q.part && q.group > 0,
+                    "EPI_NCE_* parameters not set (nce_set)");
+        TORCH_CHECK(p.epilogue == EPI_NCE_FWD ? q.pos != nullptr
+                                              : (q.lse && p.Cbase),
+                    "EPI_NCE_* outputs not set");
+        TORCH_CHECK(!nt_fast
+                    || (al(p.A.base) && al(p.B.base)
+                        && (p.epilogue == EPI_NCE_FWD
+                            || (al(p.Cbase) && p.Cld % 8 == 0))),
+                    "EPI_NCE_* full-tile path needs 16-byte aligned operands");
+    }
+    const bool nt3 = nt_fast && p.N % 256 == 0 && p.N >= 1024 && !nce;
     const bool nt5p_on = nt5p_enabled();
     // N >= 1024 only: at N=512 (2 column panels) the persistent sweep
     // measured SLOWER than the 128^2 kernel on the down-projection
@@ -312,8 +362,10 @@ void run_gemm(GemmParams& p, hipStream_t s, const torch::TensorOptions& opts,
         launch_gemm_nt_fast5p(p, s);
     else if (nt3)
         launch_gemm_nt_fast4(p, s);   // 3-ring counted-vmcnt variant
-    else if (nt_fast)
+    else if (nt_fast) {
         launch_gemm_nt_fast(p, s);
+        if (nce) g_nce_launches[0]++;
+    }
     else if (tn_tr)
         launch_gemm_tn_tr(p, g_tn_tr_variant, s);
     else if (tn_fast && p.splitk > 1)
@@ -322,8 +374,10 @@ void run_gemm(GemmParams& p, hipStream_t s, const torch::TensorOptions& opts,
         launch_gemm_tn_fast(p, s);
     else if (nn_fast)
         launch_gemm_nn_fast(p, s);
-    else
+    else {
         launch_gemm(p, s);
+        if (nce) g_nce_launches[1]++;
+    }
     check_launch();
     if (p.splitk > 1) {
         launch_gemm_finish(p, s, g_finish_wide == 1);
@@ -1396,6 +1450,168 @@ std::vector<torch::Tensor> island_sizes(torch::Tensor labels,
     return {sizes, count};
 }
 
+// ------------------------------------------------------------------ //
+// column-contrastive loss (glom_pytorch_amd/contrast.py). a, b: (M, D)
+// bf16 with unit column stride and a row stride that is a multiple of 8
+// elements (level slices of a trajectory qualify), M = B * group rows.
+// The (M, M) logits are never stored: the forward keeps one f32 per
+// (row, 128-column tile), the backward recomputes them in row blocks of at
+// most 64 MiB of bf16 G'. No atomics, no host synchronisation.
+
+static void check_nce_in(const torch::Tensor& x, const char* name) {
+    TORCH_CHECK(x.is_cuda() && x.scalar_type() == at::kBFloat16
+                && x.dim() == 2, name, " must be a 2-D bf16 GPU tensor");
+    TORCH_CHECK(x.stride(1) == 1 && x.stride(0) % 8 == 0
+                && x.size(1) % 8 == 0
+                && ((uintptr_t)x.data_ptr() & 15) == 0,
+                name, " needs unit column stride, dim and row stride "
+                "multiples of 8 and a 16-byte aligned base");
+}
+
+static float* fptr(const torch::Tensor& t) { return t.data_ptr<float>(); }
+
+static NceArgs nce_common(int64_t group, double temperature, bool all,
+                          int64_t M) {
+    NceArgs q;
+    std::memset(&q, 0, sizeof(q));
+    q.invt = (float)(1.0 / temperature);
+    q.invm = (float)(1.0 / (double)M);
+    q.group = (int)group;
+    q.all = all ? 1 : 0;
+    return q;
+}
+
+// -> {loss () f32, lse (M) f32, ra (M) f32, rb (M) f32}
+std::vector<torch::Tensor> nce_fwd(torch::Tensor a, torch::Tensor b,
+                                   int64_t group, double temperature,
+                                   bool all) {
+    check_nce_in(a, "a"); check_nce_in(b, "b");
+    TORCH_CHECK(a.sizes() == b.sizes(), "a and b must have equal shapes");
+    const int64_t M = a.size(0), D = a.size(1);
+    TORCH_CHECK(M > 0 && group > 0 && M % group == 0, "bad group size");
+    TORCH_CHECK(temperature >= 0.03, "native path needs temperature >= 0.03");
+    TORCH_CHECK(M <= (1LL << 30), "too many rows");
+    auto fo = a.options().dtype(at::kFloat);
+    hipStream_t s = cur_stream();
+    const int64_t ntn = (M + 127) / 128;
+    auto ra = torch::empty({M}, fo), rb = torch::empty({M}, fo);
+    auto lse = torch::empty({M}, fo), pos = torch::empty({M}, fo);
+    auto part = torch::empty({M, ntn}, fo);
+    auto bpart = torch::empty({NCE_MAX_PARTS}, fo);
+    auto loss = torch::empty({}, fo);
+    launch_nce_rnorm(a.data_ptr(), a.stride(0), fptr(ra), M, (int)D, s);
+    check_launch();
+    launch_nce_rnorm(b.data_ptr(), b.stride(0), fptr(rb), M, (int)D, s);
+    check_launch();
+    GemmParams p = base_params(M, M, D, LAYOUT_NT, 1, 1, 1.0f);
+    p.A.base = a.data_ptr(); p.A.ld = a.stride(0);
+    p.B.base = b.data_ptr(); p.B.ld = b.stride(0);
+    p.epilogue = EPI_NCE_FWD;
+    NceArgs q = nce_common(group, temperature, all, M);
+    q.rrow = fptr(ra); q.rcol = fptr(rb);
+    q.part = fptr(part); q.pos = fptr(pos);
+    nce_set(p, q);
+    run_gemm(p, s, a.options(), true);
+    launch_nce_loss(fptr(part), fptr(pos), fptr(lse), fptr(bpart),
+                    fptr(loss), M, (int)ntn, q.invt, s);
+    check_launch();
+    return {loss, lse, ra, rb};
+}
+
+// One side's gradient: rows = the side being differentiated (x, norms rx),
+// columns = the other side (y, ry). lse_by_col: lse belongs to the columns
+// (the dB pass, where the GEMM computes the transposed logits).
+static torch::Tensor nce_bwd_side(const torch::Tensor& go,
+                                  const torch::Tensor& x,
+                                  const torch::Tensor& y,
+                                  const torch::Tensor& rx,
+                                  const torch::Tensor& ry,
+                                  const torch::Tensor& lse, bool lse_by_col,
+                                  int64_t group, double temperature, bool all,
+                                  hipStream_t s) {
+    const int64_t M = x.size(0), D = x.size(1);
+    const int64_t ntn = (M + 127) / 128;
+    // row blocks: Rc * M * 2 bytes <= 64 MiB, whole 128-row tiles if possible
+    int64_t Rc = (32LL << 20) / M;
+    if (Rc >= 128) Rc -= Rc % 128;
+    Rc = std::max<int64_t>(1, std::min(Rc, M));
+    auto opts = x.options();
+    auto ws = torch::empty({Rc, M}, opts);
+    auto part = torch::empty({Rc, ntn}, opts.dtype(at::kFloat));
+    auto dx = torch::empty({M, D}, opts);
+    // The product G'_block @ y has a small output (Rc x D) and a long
+    // reduction (M): it runs split-K, about two blocks per CU, into f32
+    // slices that the row kernel below adds in slice order. At least two
+    // slices, so the result is rounded to bf16 once, after the row term.
+    const int64_t tiles = ((Rc + 127) / 128) * ((D + 127) / 128);
+    const int64_t sk = std::max<int64_t>(
+        2, std::min<int64_t>({16, (512 + tiles - 1) / tiles, (M + 63) / 64}));
+    auto acc = torch::empty({sk, Rc, D}, opts.dtype(at::kFloat));
+    for (int64_t r0 = 0; r0 < M; r0 += Rc) {
+        const int64_t rows = std::min(Rc, M - r0);
+        {
+            GemmParams p = base_params(rows, M, D, LAYOUT_NT, 1, 1, 1.0f);
+            p.A.base = (const uint16_t*)x.data_ptr() + r0 * x.stride(0);
+            p.A.ld = x.stride(0);
+            p.B.base = y.data_ptr(); p.B.ld = y.stride(0);
+            p.Cbase = ws.data_ptr(); p.Cld = M;
+            p.epilogue = EPI_NCE_BWD;
+            NceArgs q = nce_common(group, temperature, all, M);
+            q.rrow = fptr(rx); q.rcol = fptr(ry);
+            q.lse = fptr(lse); q.lse_col = lse_by_col ? 1 : 0;
+            q.part = fptr(part);
+            q.row0 = (int)r0;
+            nce_set(p, q);
+            run_gemm(p, s, opts, true);
+        }
+        {   // acc[slice] = G'_block (rows x M) . y (M x D) over slice's k
+            GemmParams p = base_params(rows, D, M, LAYOUT_NN, 1, 1, 1.0f);
+            p.A.base = ws.data_ptr(); p.A.ld = M;
+            p.B.base = y.data_ptr(); p.B.ld = y.stride(0);
+            p.splitk = (int)sk; p.ws = fptr(acc);
+            // same preconditions as run_gemm's nn_fast (y is aligned)
+            if (rows % 128 == 0 && D % 128 == 0 && M % 8 == 0)
+                launch_gemm_nn_sk(p, s);
+            else
+                launch_gemm(p, s);
+            check_launch();
+        }
+        launch_nce_grad_rows((uint16_t*)dx.data_ptr() + r0 * D, fptr(acc),
+                             (int)sk,
+                             (const uint16_t*)x.data_ptr() + r0 * x.stride(0),
+                             x.stride(0), fptr(part), (int)ntn,
+                             fptr(rx) + r0, fptr(go), rows, (int)D, s);
+        check_launch();
+    }
+    return dx;
+}
+
+// -> {dA (M, D) bf16, dB (M, D) bf16}; an unwanted one is empty
+std::vector<torch::Tensor> nce_bwd(torch::Tensor go, torch::Tensor a,
+                                   torch::Tensor b, torch::Tensor lse,
+                                   torch::Tensor ra, torch::Tensor rb,
+                                   int64_t group, double temperature,
+                                   bool all, bool need_a, bool need_b) {
+    check_nce_in(a, "a"); check_nce_in(b, "b");
+    TORCH_CHECK(a.sizes() == b.sizes(), "a and b must have equal shapes");
+    const int64_t M = a.size(0);
+    TORCH_CHECK(M > 0 && group > 0 && M % group == 0, "bad group size");
+    TORCH_CHECK(temperature >= 0.03, "native path needs temperature >= 0.03");
+    auto isf = [&](const torch::Tensor& t, int64_t n) {
+        return t.is_cuda() && t.is_contiguous()
+               && t.scalar_type() == at::kFloat && t.numel() == n;
+    };
+    TORCH_CHECK(isf(go, 1) && isf(lse, M) && isf(ra, M) && isf(rb, M),
+                "go / lse / ra / rb must be contiguous f32 GPU tensors");
+    hipStream_t s = cur_stream();
+    auto none = torch::empty({0}, a.options());
+    auto dA = need_a ? nce_bwd_side(go, a, b, ra, rb, lse, false, group,
+                                    temperature, all, s) : none;
+    auto dB = need_b ? nce_bwd_side(go, b, a, rb, ra, lse, true, group,
+                                    temperature, all, s) : none;
+    return {dA, dB};
+}
+
 std::string build_info() {
     return "glom_pytorch_amd HIP extension (gfx950, bf16 MFMA 16x16x32)";
 }
@@ -1481,6 +1697,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "island size at each root cell and/or island count",
           py::arg("labels"), py::arg("want_sizes") = true,
           py::arg("want_count") = true);
+    m.def("nce_fwd", &nce_fwd,
+          "column-contrastive loss forward: (M,D) bf16 a, b -> "
+          "{loss, lse, ra, rb}");
+    m.def("nce_bwd", &nce_bwd, "column-contrastive loss backward");
+    m.def("set_nce_fast", &set_nce_fast,
+          "A/B: host the EPI_NCE_* epilogues on gemm_nt_fast where eligible");
+    m.def("nce_launch_counts", &nce_launch_counts,
+          "EPI_NCE_* launches so far: {gemm_nt_fast, generic}");
     m.def("build_info", &build_info);
     m.def("bench_gemm", &bench_gemm, "raw GEMM microbench (tuning only)");
 }

@@ -15,6 +15,11 @@ enum GemmEpilogue {
     // C = gelu(bf16(acc*alpha + bias)): EPI_GELU_PAIR's out2 without the
     // pre-activation (forward-only steps; nt5p only, see run_gemm)
     EPI_GELU = 5,
+    // column-contrastive (InfoNCE) loss over cosine logits; the logits are
+    // never stored (contrast.py, gemm_epilogue_nce). Hosts: the generic
+    // kernel and gemm_nt_fast only, see run_gemm.
+    EPI_NCE_FWD = 6,   // part[i][tile] = sum_j exp(s_ij - 1/T), pos[i] = s_ii
+    EPI_NCE_BWD = 7,   // C = G' (bf16), part[i][tile] = sum_j g_ij * s_ij
 };
 
 #define GEMM_MAX_TABLE 16
@@ -87,6 +92,48 @@ struct GemmParams {
     void* Ctab[GEMM_MAX_TABLE]; long Ctabld[GEMM_MAX_TABLE];
 };
 
+// EPI_NCE_FWD / EPI_NCE_BWD arguments (single plain problem). GEMM row i is
+// logit row row0 + i, GEMM column j is logit column j;
+// s = acc * rrow[row] * rcol[col] * invt. A pair is allowed iff row == col,
+// or all, or row / group != col / group. part[i][ceil(N/128)] gets one f32
+// per (GEMM row, 128-column tile) from exactly one writer. BWD reads the
+// saved log-sum-exp by row, or by column when lse_col is set (the
+// operand-swapped dB pass), and scales g by invm = 1 / (logit rows).
+// They travel in GemmParams fields that these epilogues do not otherwise
+// use (no bias, column scale, aux, out2 or fused colsum), so the parameter
+// block keeps its size and the other kernels their code:
+//   rrow = bias_base   rcol = colscale_base   lse = aux_base
+//   part = colsum_out  pos = out2             row0 = bias_sin
+//   invt = alpha       invm = alpha2          group = npatch
+//   self_mask: bit 0 = all, bit 1 = lse_col
+struct NceArgs {
+    const float* rrow; const float* rcol; const float* lse;
+    float* part; float* pos;
+    float invt, invm;
+    int group, all, lse_col, row0, ntn;
+};
+
+static inline void nce_set(GemmParams& p, const NceArgs& a) {
+    p.bias_base = a.rrow; p.colscale_base = a.rcol; p.aux_base = a.lse;
+    p.colsum_out = a.part; p.out2 = a.pos; p.bias_sin = a.row0;
+    p.alpha = a.invt; p.alpha2 = a.invm; p.npatch = a.group;
+    p.self_mask = (a.all ? 1 : 0) | (a.lse_col ? 2 : 0);
+    p.has_bias = p.has_colscale = 0;
+}
+
+__host__ __device__ static inline NceArgs nce_get(const GemmParams& p) {
+    NceArgs a;
+    a.rrow = (const float*)p.bias_base;
+    a.rcol = (const float*)p.colscale_base;
+    a.lse = (const float*)p.aux_base;
+    a.part = p.colsum_out; a.pos = (float*)p.out2;
+    a.invt = p.alpha; a.invm = p.alpha2;
+    a.group = p.npatch; a.all = p.self_mask & 1;
+    a.lse_col = (p.self_mask >> 1) & 1;
+    a.row0 = (int)p.bias_sin; a.ntn = (p.N + 127) / 128;
+    return a;
+}
+
 void launch_gemm(const GemmParams& p, hipStream_t stream);
 // wide: re-blocked 16-byte kernel where C allows it (same bits)
 void launch_gemm_finish(const GemmParams& p, hipStream_t stream,
@@ -94,6 +141,8 @@ void launch_gemm_finish(const GemmParams& p, hipStream_t stream,
 void launch_gemm_nt_fast(const GemmParams& p, hipStream_t stream);
 void launch_gemm_tn_fast(const GemmParams& p, hipStream_t stream);
 void launch_gemm_nn_fast(const GemmParams& p, hipStream_t stream);
+// split-K NN (gemm_nn_sk.hip): f32 partials into p.ws[slice][problem][M][N]
+void launch_gemm_nn_sk(const GemmParams& p, hipStream_t stream);
 void launch_gemm_nt_fast3(const GemmParams& p, hipStream_t stream);
 void launch_gemm_nt_fast4(const GemmParams& p, hipStream_t stream);
 void launch_gemm_nt_fast5p(const GemmParams& p, hipStream_t stream);

@@ -131,6 +131,9 @@ __device__ __forceinline__ void stage_transposed(
     }
 }
 
+// NCE: the column-contrastive epilogues (EPI_NCE_FWD / EPI_NCE_BWD) as a
+// separate instantiation, so the plain kernel's code does not change.
+template <bool NCE>
 __global__ __launch_bounds__(NTHREADS) void gemm_kernel(GemmParams p) {
     __shared__ ushort_t As[BM * BKP];
     __shared__ ushort_t Bs[BN * BKP];
@@ -215,6 +218,12 @@ __global__ __launch_bounds__(NTHREADS) void gemm_kernel(GemmParams p) {
         return;
     }
 
+    if (NCE) {
+        // the K loop ended with a barrier: As is free to hold the row sums
+        gemm_epilogue_nce<false>(p, m0, n0, wm, wn, lrow, kq, acc,
+                                 (float*)As);
+        return;
+    }
     gemm_epilogue(p, pid, m0, n0, wm, wn, lrow, kq, acc);
 }
 
@@ -246,7 +255,12 @@ __global__ __launch_bounds__(NTHREADS) void gemm_finish_kernel(GemmParams p) {
 void launch_gemm(const GemmParams& p, hipStream_t stream) {
     int sk = p.splitk > 1 ? p.splitk : 1;
     dim3 grid((p.N + BN - 1) / BN, (p.M + BM - 1) / BM, p.nproblems * sk);
-    hipLaunchKernelGGL(gemm_kernel, grid, dim3(NTHREADS), 0, stream, p);
+    if (p.epilogue == EPI_NCE_FWD || p.epilogue == EPI_NCE_BWD)
+        hipLaunchKernelGGL(gemm_kernel<true>, grid, dim3(NTHREADS), 0, stream,
+                           p);
+    else
+        hipLaunchKernelGGL(gemm_kernel<false>, grid, dim3(NTHREADS), 0,
+                           stream, p);
 }
 
 // Re-blocked finish for strided (non-table) C with N % 4 == 0: one thread

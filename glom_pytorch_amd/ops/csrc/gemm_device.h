@@ -79,6 +79,107 @@ __device__ __forceinline__ void gemm_epilogue(
     }
 }
 
+// Column-contrastive loss epilogues (EPI_NCE_FWD / EPI_NCE_BWD, see gemm.h
+// and glom_pytorch_amd/contrast.py). The 128x128 tile of cosine logits
+//     s = acc * rrow[row] * rcol[col] / temperature
+// lives only in the accumulators. Both epilogues reduce one f32 per tile row
+// over the tile's columns: FWD sum_j [allowed] exp(s - 1/T) (|s| <= 1/T, so
+// the fixed shift replaces an online maximum), BWD sum_j g*s with
+//     g = ([allowed] exp(s - lse) - [row == col]) / M,
+// and BWD stores G' = g * rrow * rcol / T as bf16 C. The allowed mask is per
+// element (image boundaries fall inside tiles). Reduction order is fixed:
+// j16 = 0..3 in the thread, xor butterfly over the 16 column lanes, then
+// wave column-half 0 + half 1 through `scratch` -> exactly one plain store
+// per (row, column tile), no atomics.
+// Every thread of the block must call this (it holds barriers); `scratch`
+// may alias the operand tiles, the caller's K loop ends with a barrier.
+// Needs 2*128*4 bytes of scratch, FULL another 128*EPI_LDS_ROW*2 behind it.
+// FULL: whole tile in range, C 16-byte aligned with Cld % 8 == 0 -> G' is
+// packed in LDS and streamed out as full lines (as gemm_epilogue_lds).
+#define NCE_LDS_ROW 136   // = EPI_LDS_ROW (defined below)
+
+template <bool FULL>
+__device__ __forceinline__ void gemm_epilogue_nce(
+        const GemmParams& p, int m0, int n0, int wm, int wn, int lrow, int kq,
+        const f32x4 acc[4][4], float* scratch) {
+    const bool bwd = p.epilogue == EPI_NCE_BWD;
+    const NceArgs q = nce_get(p);
+    ushort_t* Cp = (ushort_t*)p.Cbase;
+    ushort_t* ctile = (ushort_t*)(scratch + 256);
+    const float invt = q.invt;
+
+    // column factors of this thread's 4 columns
+    int gcv[4], cgrp[4];
+    float rcv[4], lsec[4];
+#pragma unroll
+    for (int j16 = 0; j16 < 4; j16++) {
+        int gc = n0 + wn + j16 * 16 + lrow;
+        bool ok = FULL || gc < p.N;
+        gcv[j16] = ok ? gc : -1;
+        cgrp[j16] = gc / q.group;
+        rcv[j16] = ok ? q.rcol[gc] * invt : 0.f;
+        lsec[j16] = (ok && bwd && q.lse_col) ? q.lse[gc] : 0.f;
+    }
+
+#pragma unroll
+    for (int i16 = 0; i16 < 4; i16++) {
+#pragma unroll
+        for (int r = 0; r < 4; r++) {
+            const int li = wm + i16 * 16 + kq * 4 + r;       // 0..127
+            const int i = m0 + li;                           // GEMM row
+            const bool rok = FULL || i < p.M;
+            const int gr = q.row0 + i;                   // logit row
+            const int rgrp = gr / q.group;
+            const float rr = rok ? q.rrow[gr] : 0.f;
+            const float lser =
+                (rok && bwd && !q.lse_col) ? q.lse[gr] : 0.f;
+            float sum = 0.f;
+#pragma unroll
+            for (int j16 = 0; j16 < 4; j16++) {
+                const int gc = gcv[j16];
+                const bool ok = rok && gc >= 0;
+                const bool diag = ok && gr == gc;
+                const bool allowed =
+                    ok && (diag || q.all || rgrp != cgrp[j16]);
+                const float scale = rr * rcv[j16];
+                const float s = acc[i16][j16][r] * scale;
+                if (!bwd) {
+                    sum += allowed ? expf(s - invt) : 0.f;
+                    if (diag) q.pos[gr] = s;
+                } else {
+                    const float lse = q.lse_col ? lsec[j16] : lser;
+                    float g = allowed ? expf(s - lse) : 0.f;
+                    g = (g - (diag ? 1.f : 0.f)) * q.invm;
+                    sum += ok ? g * s : 0.f;
+                    const ushort_t o = f2bf(g * scale);
+                    if (FULL)
+                        ctile[li * NCE_LDS_ROW + wn + j16 * 16 + lrow] = o;
+                    else if (ok)
+                        Cp[(long)i * p.Cld + gc] = o;
+                }
+            }
+            sum += __shfl_xor(sum, 1);
+            sum += __shfl_xor(sum, 2);
+            sum += __shfl_xor(sum, 4);
+            sum += __shfl_xor(sum, 8);
+            if (lrow == 0) scratch[(wn >> 6) * 128 + li] = sum;
+        }
+    }
+    __syncthreads();
+    const int t = threadIdx.x;
+    if (t < 128 && (FULL || m0 + t < p.M))
+        q.part[(long)(m0 + t) * q.ntn + n0 / 128] =
+            scratch[t] + scratch[128 + t];
+    if (FULL && bwd) {
+        const int li = t >> 1, half = (t & 1) * 64;
+        ushort_t* crow = Cp + (long)(m0 + li) * p.Cld + n0 + half;
+        const ushort_t* srow = ctile + li * NCE_LDS_ROW + half;
+#pragma unroll
+        for (int c = 0; c < 8; c++)
+            *(uint4v*)(crow + c * 8) = *(const uint4v*)(srow + c * 8);
+    }
+}
+
 // Full-tile epilogue with LDS-staged stores: the MFMA D-fragment layout
 // (col = lane&15, rows scattered) makes direct global stores 2-byte
 // partial-line writes (read-modify-write amplified in L2). Instead the

@@ -26,18 +26,12 @@
 #include "common.h"
 #include "gemm.h"
 #include "gemm_device.h"
+#include "gemm_stage.h"
 
 #define BM 128
 #define BN 128
 #define FBK 64
 #define NTHREADS 256
-
-// LDS bank swizzle: 16B-granule index in a 128B row is XORed with
-// swz_row(row); includes row bit 3 so writes/reads 8 rows apart do not
-// collide on the same 16B slot of the 256B bank row.
-__device__ __forceinline__ int swz_row(int row) {
-    return (row ^ (row >> 3)) & 7;
-}
 
 // Fused colsum partial (GemmParams::colsum_out, layout [M/64][N]): the one
 // writer of rows [row0, row0 + 64*nslots) x column `col` stores its sum in
@@ -77,6 +71,9 @@ __device__ __forceinline__ void stage_glds(
     }
 }
 
+// NCE: the column-contrastive epilogues (EPI_NCE_FWD / EPI_NCE_BWD) as a
+// separate instantiation, so the plain kernel's code does not change.
+template <bool NCE>
 __global__ __launch_bounds__(NTHREADS) void gemm_nt_fast_kernel(GemmParams p) {
     // ONE shared array: a second __shared__ object makes hipcc emit
     // s_waitcnt vmcnt(0) before the first ds_read of every k-step of a
@@ -155,37 +152,12 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nt_fast_kernel(GemmParams p) {
         __syncthreads();   // drains the in-flight DMA (vmcnt0) + buffer reuse
         cur ^= 1;
     }
+    if (NCE) {
+        gemm_epilogue_nce<true>(p, m0, n0, wm, wn, lrow, kq, acc,
+                                (float*)smem);
+        return;
+    }
     gemm_epilogue_lds(p, pid, m0, n0, wm, wn, lrow, kq, acc, smem);
-}
-
-// Transpose-stage one operand tile: source rows = reduction slice
-// [t0, t0+64) (row stride ld), cols = output-dim slice [c0, c0+128).
-// 128 threads per operand; thread (mb, cb) loads an 8(m) x 8(c) block and
-// writes 8 column-vectors of 8 bf16 via ds_write_b128 into the swizzled
-// [col][m] image (row length 64 elements = 128 B).
-__device__ __forceinline__ void stage_repack(
-        ushort_t* lds, const ushort_t* src, long ld, int t0, int c0,
-        int kend, int tid128) {
-    int cb = tid128 & 15;   // 16 col-blocks of 8
-    int mb = tid128 >> 4;   // 8 m-blocks of 8
-    union { uint4v v; ushort_t u[8]; } rowv[8];
-#pragma unroll
-    for (int r = 0; r < 8; r++) {
-        int m = t0 + mb * 8 + r;
-        if (m < kend)
-            rowv[r].v = *(const uint4v*)(src + (long)m * ld + c0 + cb * 8);
-        else
-            rowv[r].v = 0;
-    }
-#pragma unroll
-    for (int e = 0; e < 8; e++) {
-        union { uint4v v; ushort_t u[8]; } col;
-#pragma unroll
-        for (int r = 0; r < 8; r++) col.u[r] = rowv[r].u[e];
-        int row = cb * 8 + e;                       // output-dim index
-        int off = (mb * 8) ^ (swz_row(row) << 3);   // swizzled m offset
-        *(uint4v*)&lds[row * FBK + off] = col.v;
-    }
 }
 
 __global__ __launch_bounds__(NTHREADS) void gemm_tn_fast_kernel(GemmParams p) {
@@ -284,8 +256,12 @@ __global__ __launch_bounds__(NTHREADS) void gemm_tn_fast_kernel(GemmParams p) {
 
 void launch_gemm_nt_fast(const GemmParams& p, hipStream_t stream) {
     dim3 grid(p.N / BN, p.M / BM, p.nproblems);
-    hipLaunchKernelGGL(gemm_nt_fast_kernel, grid, dim3(NTHREADS), 0, stream,
-                       p);
+    if (p.epilogue == EPI_NCE_FWD || p.epilogue == EPI_NCE_BWD)
+        hipLaunchKernelGGL(gemm_nt_fast_kernel<true>, grid, dim3(NTHREADS), 0,
+                           stream, p);
+    else
+        hipLaunchKernelGGL(gemm_nt_fast_kernel<false>, grid, dim3(NTHREADS),
+                           0, stream, p);
 }
 
 void launch_gemm_tn_fast(const GemmParams& p, hipStream_t stream) {
@@ -299,27 +275,6 @@ void launch_gemm_tn_fast(const GemmParams& p, hipStream_t stream) {
 // NN fast kernel (attention AV / dq): A row-major [M][K] staged as a
 // plain swizzled copy; B row-major [K][N] transpose-staged with the
 // 8x8 register repack. Single LDS buffer, two barriers per K-step.
-
-__device__ __forceinline__ void stage_copy128(
-        ushort_t* lds, const ushort_t* src, long ld, int r0, int k0,
-        int maxK, int tid128) {
-    // 128 threads stage a 128x64 tile: thread t handles rows t, t+... no:
-    // 1024 chunks of 8 elements / 128 threads = 8 chunks each
-#pragma unroll
-    for (int cc = 0; cc < 8; cc++) {
-        int c = tid128 * 8 + cc;
-        int row = c >> 3;
-        int g = c & 7;
-        int gk = k0 + g * 8;
-        union { uint4v v; ushort_t u[8]; } t;
-        if (gk + 7 < maxK)
-            t.v = *(const uint4v*)(src + (long)(r0 + row) * ld + gk);
-        else
-            t.v = 0;
-        int off = (g * 8) ^ (swz_row(row) << 3);
-        *(uint4v*)&lds[row * FBK + off] = t.v;
-    }
-}
 
 __global__ __launch_bounds__(NTHREADS) void gemm_nn_fast_kernel(GemmParams p) {
     __shared__ ushort_t smem[128 * EPI_LDS_ROW];   // >= As+Bs (2*8192)

@@ -69,6 +69,38 @@ class LinearFixedBiasGradFn(torch.autograd.Function):
         return dx, dw, db
 
 
+class ContrastFn(torch.autograd.Function):
+    """Column-contrastive loss (``glom_pytorch_amd.contrast``) on (M, D)
+    bf16 row matrices, ``M = B * group``. Forward: two reciprocal-norm
+    launches, one NT GEMM whose EPI_NCE_FWD epilogue reduces
+    ``exp(s - 1/T)`` per (row, column tile) without storing the logits, and
+    a fixed-order finish. Backward: per row block, EPI_NCE_BWD recomputes
+    the logits and writes ``G'`` (bf16, <= 64 MiB), a split-K NN GEMM forms
+    ``G' @ other`` in f32 slices and a row kernel adds them in order,
+    applies the normalisation term and the incoming gradient and rounds to
+    bf16 once. Saved: the inputs, ``lse`` and both norm vectors."""
+
+    @staticmethod
+    def forward(ctx, a, b, group, temperature, all_negatives):
+        ext = _load_extension()
+        loss, lse, ra, rb = ext.nce_fwd(a, b, group, temperature,
+                                        all_negatives)
+        ctx.save_for_backward(a, b, lse, ra, rb)
+        ctx.cfg = (group, temperature, all_negatives)
+        return loss
+
+    @staticmethod
+    def backward(ctx, go):
+        ext = _load_extension()
+        a, b, lse, ra, rb = ctx.saved_tensors
+        need_a, need_b = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        go = go.to(torch.float32).reshape(1).contiguous()
+        dA, dB = ext.nce_bwd(go, a, b, lse, ra, rb, *ctx.cfg, need_a,
+                             need_b)
+        return (dA if need_a else None), (dB if need_b else None), \
+            None, None, None
+
+
 class TrajectoryFn(torch.autograd.Function):
     """return_all trajectory (reference glom_pytorch.py:126,145-148)
     without the torch.stack copy: every step already wrote its output into

@@ -52,7 +52,9 @@ class DenoisingTrainer:
     def __init__(self, model, *, lr=3e-4, noise_std=1.0, decode_step=7,
                  grad_clip=1.0, distributed=False, bucket_bytes=16 << 20,
                  process_group=None, graph_step=True, overlap_tail=True,
-                 micro_batches=1, log_path=None):
+                 micro_batches=1, log_path=None, contrast_weight=0.0,
+                 contrast_level=-1, contrast_temperature=0.1,
+                 contrast_negatives="other_images"):
         """``process_group``: the group whose ranks are data-parallel
         replicas (default: the global group). For 2-D DP x SP meshes pass
         the DP subgroup here — BucketedDDP AVERAGES over its group, which
@@ -62,7 +64,30 @@ class DenoisingTrainer:
         ``graph_step``: hipGraph-capture the whole training step on the
         native bf16 GPU path (keyed on batch shape + iters) and replay it;
         falls back to eager launches automatically if capture fails.
-        Disable with graph_step=False or GLOM_NO_GRAPH_STEP=1."""
+        Disable with graph_step=False or GLOM_NO_GRAPH_STEP=1.
+
+        ``contrast_weight`` (default 0.0 = the plain denoising step, launch
+        for launch): when > 0 every step noises the batch twice, runs ONE
+        forward on the 2B concatenation, averages the denoising loss over
+        both views and adds ``contrast_weight *
+        column_contrastive_loss(top_a, top_b)`` between the two views'
+        level ``contrast_level`` at the decode step
+        (``glom_pytorch_amd.contrast``; ``contrast_temperature`` and
+        ``contrast_negatives`` are passed through). The settings are
+        constructor constants, so captured graphs stay keyed on batch shape
+        and iters. Micro-batching with the term on is not implemented
+        (negatives would have to cross chunks): ``step`` raises
+        ``NotImplementedError``."""
+        from glom_pytorch_amd.contrast import NEGATIVES
+        if contrast_weight < 0 or not contrast_temperature > 0:
+            raise ValueError("contrast_weight must be >= 0 and "
+                             "contrast_temperature > 0")
+        if contrast_negatives not in NEGATIVES:
+            raise ValueError(f"contrast_negatives must be one of {NEGATIVES}")
+        self.contrast_weight = float(contrast_weight)
+        self.contrast_level = int(contrast_level)
+        self.contrast_temperature = float(contrast_temperature)
+        self.contrast_negatives = contrast_negatives
         self.model = model
         self.dim = model.dim
         self.decode_step = decode_step
@@ -154,6 +179,8 @@ class DenoisingTrainer:
                 and os.environ.get("GLOM_FORCE_EAGER", "0") != "1")
 
     def _eager_step(self, img: torch.Tensor, iters: int) -> torch.Tensor:
+        if self.contrast_weight > 0:
+            return self._contrast_step(img, iters)
         m = self.micro_batches
         if (m > 1 and img.is_cuda and img.shape[0] % m == 0
                 and not getattr(self.model, "force_eager", False)):
@@ -188,6 +215,59 @@ class DenoisingTrainer:
                 for mw, q in zip(self.master, self._params):
                     # None (not stale) when the param got no grad this
                     # step, e.g. init_levels on the stateful path
+                    mw.grad = q.grad.float() if q.grad is not None else None
+                if self.grad_clip:
+                    torch.nn.utils.clip_grad_norm_(self.master,
+                                                   self.grad_clip)
+                self.opt.step()
+                for mw, q in zip(self.master, self._params):
+                    q.data.copy_(mw)
+        else:
+            if self.grad_clip:
+                torch.nn.utils.clip_grad_norm_(
+                    [q for g in self.opt.param_groups for q in g["params"]],
+                    self.grad_clip)
+            self.opt.step()
+        return loss.detach()
+
+    def _contrast_step(self, img: torch.Tensor, iters: int) -> torch.Tensor:
+        """Denoising step over two independently noised views of the batch
+        (one 2B forward) plus the weighted column-contrastive term between
+        the views. Both losses read trajectory time t only, so grad_iters
+        and the overlapped tail stay valid as in ``_eager_step``."""
+        from glom_pytorch_amd.contrast import column_contrastive_loss
+        if self.micro_batches > 1:
+            raise NotImplementedError(
+                "contrast_weight > 0 does not support micro_batches > 1")
+        t = min(self.decode_step, iters)
+        B = img.shape[0]
+        self.opt.zero_grad(set_to_none=True)
+        noised = torch.cat(
+            (img + torch.randn_like(img) * self.noise_std,
+             img + torch.randn_like(img) * self.noise_std))
+        overlap = (self.overlap_tail and img.is_cuda
+                   and not getattr(self.model, "force_eager", False))
+        all_levels = self.model(noised, iters=iters, return_all=True,
+                                grad_iters=t, overlap_tail=overlap)
+        recon = self.decoder(all_levels[t, :, :, -1])
+        clean = torch.cat((img, img))
+        loss = F.mse_loss(recon.float(), clean.float())
+        lvl = all_levels[t, :, :, self.contrast_level]
+        loss = loss + self.contrast_weight * column_contrastive_loss(
+            lvl[:B], lvl[B:], temperature=self.contrast_temperature,
+            negatives=self.contrast_negatives)
+        loss.backward()
+        if self.distributed:
+            self.ddp_model.finalize()
+            self.ddp_dec.finalize()
+        if overlap:
+            from glom_pytorch_amd.ops.functional import join_tail_stream
+            join_tail_stream()
+        if self.fused_opt is not None:
+            self.fused_opt.step()
+        elif self.master is not None:
+            with torch.no_grad():
+                for mw, q in zip(self.master, self._params):
                     mw.grad = q.grad.float() if q.grad is not None else None
                 if self.grad_clip:
                     torch.nn.utils.clip_grad_norm_(self.master,

@@ -19,9 +19,11 @@ ext = CUDAExtension(
         "glom_pytorch_amd/ops/csrc/bindings.cpp",
         "glom_pytorch_amd/ops/csrc/gemm.hip",
         "glom_pytorch_amd/ops/csrc/gemm_fast.hip",
+        "glom_pytorch_amd/ops/csrc/gemm_nn_sk.hip",
         "glom_pytorch_amd/ops/csrc/aux_kernels.hip",
         "glom_pytorch_amd/ops/csrc/native_ops.hip",
         "glom_pytorch_amd/ops/csrc/island_kernels.hip",
+        "glom_pytorch_amd/ops/csrc/contrast_kernels.hip",
     ],
     extra_compile_args={
         "cxx": ["-O3", "-std=c++17"],
