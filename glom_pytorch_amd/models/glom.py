@@ -195,7 +195,8 @@ class Glom(nn.Module):
                 levels: torch.Tensor | None = None,
                 return_all: bool = False,
                 grad_iters: int | None = None,
-                overlap_tail: bool = False) -> torch.Tensor:
+                overlap_tail: bool = False,
+                loss_level_min: int | None = None) -> torch.Tensor:
         """grad_iters (extension kwarg, default None = exact reference
         autograd graph): run iterations >= grad_iters under no_grad.
         Forward values are unchanged; use when the loss only reads
@@ -205,7 +206,16 @@ class Glom(nn.Module):
         runs those iterations on a side stream so they overlap the
         caller's backward; the caller MUST then call
         ``ops.functional.join_tail_stream()`` before reading the tail's
-        trajectory slices or mutating weights."""
+        trajectory slices or mutating weights.
+
+        ``loss_level_min`` (extension kwarg, needs ``grad_iters``; default
+        None = today's behaviour) is a promise: the loss reads the
+        trajectory only at time ``grad_iters`` and only at levels >=
+        ``loss_level_min``. The native backward then skips, per iteration,
+        the level groups whose gradient is exactly zero (the level cone,
+        docs/ARCHITECTURE.md). Values and gradients are unchanged; the
+        eager path ignores it. ``ops.set_check_level_cone(True)`` verifies
+        the promise on every backward."""
         if img.dim() != 4 or img.shape[1] != 3:
             raise ValueError(f"expected image batch (b, 3, H, W), got {tuple(img.shape)}")
         iters = iters if iters is not None else 2 * self.levels
@@ -220,9 +230,10 @@ class Glom(nn.Module):
             return native_forward(self, img, iters=iters, levels=levels,
                                   return_all=return_all,
                                   grad_iters=grad_iters,
-                                  overlap_tail=overlap_tail)
+                                  overlap_tail=overlap_tail,
+                                  loss_level_min=loss_level_min)
         return self._eager_forward(img, iters, levels, return_all,
-                                   grad_iters)
+                                   grad_iters, loss_level_min)
 
     def enable_graphs(self):
         """hipGraph-capture the T-step loop for inference: each distinct
@@ -267,7 +278,8 @@ class Glom(nn.Module):
     # compare the HIP engine against it.
 
     def _eager_forward(self, img, iters, levels, return_all,
-                       grad_iters=None):
+                       grad_iters=None, loss_level_min=None):
+        # loss_level_min: accepted and ignored (autograd computes the zeros)
         b = img.shape[0]
         tokens = self.image_to_tokens(img)
         n = tokens.shape[1]

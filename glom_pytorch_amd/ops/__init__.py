@@ -49,9 +49,20 @@ def available() -> bool:
 
 
 def native_forward(model, img, iters, levels=None, return_all=False,
-                   grad_iters=None, overlap_tail=False):
+                   grad_iters=None, overlap_tail=False, loss_level_min=None):
     """Run Glom.forward on the CDNA4 HIP engine (bf16, gfx950)."""
     from glom_pytorch_amd.ops.functional import glom_forward
     return glom_forward(model, img, iters=iters, levels=levels,
                         return_all=return_all, grad_iters=grad_iters,
-                        overlap_tail=overlap_tail)
+                        overlap_tail=overlap_tail,
+                        loss_level_min=loss_level_min)
+
+
+def set_check_level_cone(on: bool) -> None:
+    """Level-cone check mode: before each step's backward, verify with one
+    host sync that the gradient is zero below the level ``loss_level_min``
+    promised, and raise ``RuntimeError`` naming the iteration and level if
+    not. Off by default (``GLOM_CHECK_LEVEL_CONE=1`` turns it on); cannot
+    run under stream capture."""
+    from glom_pytorch_amd.ops import functional
+    functional.set_check_level_cone(on)

@@ -7,13 +7,17 @@ void launch_rnorm(const void* levels, float* out, int B, int N, int L, int d,
                   hipStream_t s);
 void launch_softmax_fwd(const void* scores, void* probs, const bool* mask,
                         int nprob, int N, int self_mask, hipStream_t s);
+// nprob live problems: levels [l_lo, L) of each batch entry, addressed in
+// buffers that keep all L levels (defaults: every problem, as laid out)
 void launch_softmax_bwd(const void* P, const void* dP, const float* rnorm,
                         void* dS, void* dSr, const bool* mask, int nprob,
-                        int N, int self_mask, float alpha, hipStream_t s);
+                        int N, int self_mask, float alpha, hipStream_t s,
+                        int L = 1, int l_lo = 0);
+// rows of levels [l_lo, L) only; the other rows of `out` are not written
 void launch_knorm_combine(const void* dkhat, const void* lev,
                           const float* rnorm, const void* dv, const void* dq,
                           void* out, int B, int N, int L, int d,
-                          hipStream_t s);
+                          hipStream_t s, int l_lo = 0);
 void launch_mix_fwd(const void* prev, const void* bu, const void* td,
                     const void* cons, void* out, long total, int L, int d,
                     hipStream_t s);

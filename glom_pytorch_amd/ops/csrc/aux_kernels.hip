@@ -147,12 +147,16 @@ __global__ __launch_bounds__(NTHREADS) void k_softmax_bwd(
         const ushort_t* __restrict__ P, const ushort_t* __restrict__ dP,
         const float* __restrict__ rnorm, ushort_t* __restrict__ dS,
         ushort_t* __restrict__ dSr, const bool* __restrict__ nonlocal_mask,
-        int nprob, int N, int self_mask, float alpha) {
+        int nprob, int N, int self_mask, float alpha, int L, int l_lo) {
+    // nprob counts the live problems: levels [l_lo, L) of every batch
+    // entry; the buffers keep all L levels per entry (problem b * L + l)
     long row = (long)blockIdx.x * WPB + threadIdx.x / WAVE;
     if (row >= (long)nprob * N) return;
     int lane = threadIdx.x % WAVE;
     int i = row % N;
     long p = row / N;
+    p = (p / (L - l_lo)) * L + l_lo + p % (L - l_lo);
+    row = p * N + i;
     const ushort_t* pr = P + row * N;
     const ushort_t* dpr = dP + row * N;
     const float* rn = rnorm + p * N;
@@ -208,14 +212,17 @@ __global__ __launch_bounds__(NTHREADS) void k_knorm_combine(
         const ushort_t* __restrict__ dkhat, const ushort_t* __restrict__ lev,
         const float* __restrict__ rnorm, const ushort_t* __restrict__ dv,
         const ushort_t* __restrict__ dq, ushort_t* __restrict__ out,
-        int B, int N, int L, int d) {
+        int B, int N, int L, int d, int l_lo) {
+    // one wave per live row: levels [l_lo, L) of every (b, n)
     long row = (long)blockIdx.x * WPB + threadIdx.x / WAVE;
-    long total = (long)B * N * L;
+    const int Ll = L - l_lo;
+    long total = (long)B * N * Ll;
     if (row >= total) return;
     int lane = threadIdx.x % WAVE;
-    int l = row % L;
-    long n = (row / L) % N;
-    long b = row / ((long)N * L);
+    int l = l_lo + row % Ll;
+    long n = (row / Ll) % N;
+    long b = row / ((long)N * Ll);
+    row = (b * N + n) * L + l;
     const ushort_t* dkh = dkhat + ((b * L + l) * N + n) * (long)d;
     const ushort_t* x = lev + row * d;
     float r = rnorm[(b * L + l) * N + n];
@@ -361,23 +368,25 @@ void launch_softmax_fwd(const void* scores, void* probs, const bool* mask,
 
 void launch_softmax_bwd(const void* P, const void* dP, const float* rnorm,
                         void* dS, void* dSr, const bool* mask, int nprob,
-                        int N, int self_mask, float alpha, hipStream_t s) {
+                        int N, int self_mask, float alpha, hipStream_t s,
+                        int L, int l_lo) {
     long rows = (long)nprob * N;
     hipLaunchKernelGGL(k_softmax_bwd, dim3(cdiv(rows, WPB)), dim3(NTHREADS),
                        0, s, (const ushort_t*)P, (const ushort_t*)dP, rnorm,
                        (ushort_t*)dS, (ushort_t*)dSr, mask, nprob, N,
-                       self_mask, alpha);
+                       self_mask, alpha, L, l_lo);
 }
 
 void launch_knorm_combine(const void* dkhat, const void* lev,
                           const float* rnorm, const void* dv, const void* dq,
                           void* out, int B, int N, int L, int d,
-                          hipStream_t s) {
-    long rows = (long)B * N * L;
+                          hipStream_t s, int l_lo) {
+    long rows = (long)B * N * (L - l_lo);
+    if (rows <= 0) return;
     hipLaunchKernelGGL(k_knorm_combine, dim3(cdiv(rows, WPB)), dim3(NTHREADS),
                        0, s, (const ushort_t*)dkhat, (const ushort_t*)lev,
                        rnorm, (const ushort_t*)dv, (const ushort_t*)dq,
-                       (ushort_t*)out, B, N, L, d);
+                       (ushort_t*)out, B, N, L, d, l_lo);
 }
 
 void launch_mix_fwd(const void* prev, const void* bu, const void* td,

@@ -240,8 +240,15 @@ void set_nce_fast(bool on) { g_nce_fast = on ? 1 : 0; }
 // output, K = B*N tokens; partial f32 slabs summed by gemm_finish), and
 // otherwise falls back to the generic predicated kernel.
 // `lds_ok` asserts every A/B row stride (incl. table entries) is %8 == 0.
+// `gate_problems` (0 = p.nproblems): the problem count the grid gates
+// (split-K factor, nt5p and nt8p minimum grids) are judged by. Callers that
+// launch only the live tail of a grouped problem (level cone, see
+// grouped_ff_bwd) pass the full group count, so every live group is served
+// by the kernel and split-K factor the full call gives it: same bits. It
+// stays on the host; the kernels see only the live problems.
 void run_gemm(GemmParams& p, hipStream_t s, const torch::TensorOptions& opts,
-              bool lds_ok) {
+              bool lds_ok, long gate_problems = 0) {
+    const long gate_np = gate_problems > 0 ? gate_problems : p.nproblems;
     const bool no_xform = !(p.A.flags & (OP_GELU | OP_POS))
                           && !(p.B.flags & (OP_GELU | OP_POS));
     const bool nce_generic = !g_nce_fast && (p.epilogue == EPI_NCE_FWD
@@ -257,7 +264,7 @@ void run_gemm(GemmParams& p, hipStream_t s, const torch::TensorOptions& opts,
     p.splitk = 1;
     p.ws = nullptr;
     torch::Tensor ws;
-    long blocks = ((p.N + 127) / 128) * ((p.M + 127) / 128) * p.nproblems;
+    long blocks = ((p.N + 127) / 128) * ((p.M + 127) / 128) * gate_np;
     if (p.layout == LAYOUT_TN && p.epilogue == EPI_NONE && !p.has_bias
         && !p.has_colscale && blocks < 1024 && p.K >= 4096) {
         long sk = std::min<long>(16, std::max<long>(1, 2048 / blocks));
@@ -297,7 +304,7 @@ void run_gemm(GemmParams& p, hipStream_t s, const torch::TensorOptions& opts,
     // 192-block grids) the persistent sweep beats nt3 by ~20% (3172 ->
     // 3812 frames/s); training grids are >= 768 and unaffected.
     const bool nt5p = nt5p_on && nt3 && p.M % 512 == 0
-                      && (long)(p.N / 256) * (p.M / 512) * p.nproblems
+                      && (long)(p.N / 256) * (p.M / 512) * gate_np
                          >= nt5p_min_grid()
                       && !(p.Cflags & OP_TABLE)
                       && (p.epilogue == EPI_NONE
@@ -331,7 +338,7 @@ void run_gemm(GemmParams& p, hipStream_t s, const torch::TensorOptions& opts,
                       && !(p.Cflags & OP_TABLE)
                       && (p.epilogue == EPI_NONE
                           || p.epilogue == EPI_GELUGRAD)
-                      && (long)(p.N / 256) * (p.M / 256) * p.nproblems >= 256;
+                      && (long)(p.N / 256) * (p.M / 256) * gate_np >= 256;
     // whole K-steps only: K % 64 == 0 makes every split-K slice (`per` is
     // a multiple of 64) a whole number of stages; K % 8 tails stay on the
     // repack kernels. 16-byte DMA sources need 16-byte-aligned bases.
@@ -396,6 +403,44 @@ GemmParams base_params(int64_t M, int64_t N, int64_t K, int layout,
     p.alpha = alpha;
     p.epilogue = EPI_NONE;
     return p;
+}
+
+// ------------------------------------------------------------------ //
+// Level cone (docs/ARCHITECTURE.md "Level cone"): the backward ops take the
+// first live group / level (`g_lo`, `l_lo`, default 0 = everything). The
+// caller promises that the incoming gradient is exactly zero below it, so
+// the GEMMs run on the live tail only (bases and tables offset, nproblems
+// shrunk, gates judged by the full count) and what the dead groups would
+// have produced, zeros, is filled in. Shapes never change.
+
+// element `off` of a bf16 tensor
+void* u16_at(const torch::Tensor& t, int64_t off) {
+    return (void*)((uint16_t*)t.data_ptr() + off);
+}
+
+void zero_fill(void* ptr, int64_t bytes, hipStream_t s) {
+    if (bytes <= 0) return;
+    hipError_t e = hipMemsetAsync(ptr, 0, (size_t)bytes, s);
+    TORCH_CHECK(e == hipSuccess, "zero fill failed: ", hipGetErrorString(e));
+}
+
+// Level slices of the FF data gradient dLevels (B,N,L,d) that no live
+// group's dX writes. Bottom-up group g >= 1 writes slice g-1 (group 0
+// writes dTokens), top-down group g writes slice g+1.
+void zero_unwritten_dx(void* dLevels, int64_t BN, int64_t L, int64_t d,
+                       int64_t mode, int64_t g_lo, hipStream_t s) {
+    if (mode == 0) {
+        // written: [max(g_lo, 1) - 1, L - 1); the top slice never is
+        launch_zero_slices(dLevels, BN, (int)L, (int)d, 0,
+                           (int)std::max<int64_t>(g_lo, 1) - 1, s);
+        check_launch();
+        launch_zero_slice(dLevels, BN, (int)L, (int)d, (int)L - 1, s);
+        check_launch();
+    } else {
+        launch_zero_slices(dLevels, BN, (int)L, (int)d, 0,
+                           (int)std::min<int64_t>(g_lo + 1, L), s);
+        check_launch();
+    }
 }
 
 // ------------------------------------------------------------------ //
@@ -506,7 +551,8 @@ std::vector<torch::Tensor> grouped_ff_bwd(
         torch::Tensor Hact, int64_t mode,
         c10::optional<torch::Tensor> w1t_opt = c10::nullopt,
         c10::optional<torch::Tensor> w2t_opt = c10::nullopt,
-        c10::optional<torch::Tensor> td_in_opt = c10::nullopt) {
+        c10::optional<torch::Tensor> td_in_opt = c10::nullopt,
+        int64_t g_lo = 0) {
     CHECK_IN(dY); CHECK_IN(levels); CHECK_IN(w1); CHECK_IN(w2); CHECK_IN(Hpre);
     CHECK_IN(Hact);
     const int64_t B = levels.size(0), N = levels.size(1),
@@ -514,18 +560,41 @@ std::vector<torch::Tensor> grouped_ff_bwd(
     const int64_t G = (mode == 0) ? L : L - 1;
     const int64_t m4 = w1.size(0) / G;
     const int64_t M = B * N;
+    TORCH_CHECK(g_lo >= 0 && g_lo <= G, "g_lo out of range");
+    // live groups [g_lo, G): Ga of them, the first at element offsets
+    // g_lo * (group stride) into every per-group operand
+    const int64_t Ga = G - g_lo;
     auto opts = levels.options();
     hipStream_t s = cur_stream();
 
-    auto dHpre = torch::empty({G, M, m4}, opts);
     // the scattered dX GEMM writes every level slice except one (mode 0:
-    // the top slice, which only the top-down path feeds; mode 1: slice 0);
-    // zero just that slice instead of a full-tensor fill
+    // the top slice, which only the top-down path feeds; mode 1: slice 0)
+    // and those of the dead groups; zero just these instead of a
+    // full-tensor fill
     auto dLevels = torch::empty({B, N, L, d}, opts);
-    launch_zero_slice(dLevels.data_ptr(), B * N, (int)L, (int)d,
-                      mode == 0 ? (int)L - 1 : 0, s);
-    check_launch();
+    zero_unwritten_dx(dLevels.data_ptr(), B * N, L, d, mode, g_lo, s);
     torch::Tensor dTokens;
+    auto dW1 = torch::empty({G * m4, d}, opts);
+    auto dW2 = torch::empty({G * d, m4}, opts);
+    auto dB1 = torch::empty({G * m4}, opts);
+    auto dB2 = torch::empty({G * d}, opts);
+    zero_fill(dW1.data_ptr(), g_lo * m4 * d * 2, s);
+    zero_fill(dW2.data_ptr(), g_lo * d * m4 * 2, s);
+    zero_fill(dB1.data_ptr(), g_lo * m4 * 2, s);
+    if (mode == 0) {
+        dTokens = torch::empty({B, N, d}, opts);
+        if (g_lo > 0) zero_fill(dTokens.data_ptr(), M * d * 2, s);
+    } else {
+        dTokens = torch::empty({0}, opts);
+    }
+    if (Ga == 0) {
+        // nothing live: the fills are the whole result
+        zero_fill(dB2.data_ptr(), G * d * 2, s);
+        return {dTokens, dLevels, dW1, dB1, dW2, dB2};
+    }
+    TORCH_CHECK(Hpre.numel() == G * M * m4 && Hact.numel() == G * M * m4,
+                "Hpre / Hact must be (G, M, m4)");
+    auto dHpre = torch::empty({G, M, m4}, opts);
 
     // per-group weight transposes turn the NN data grads into NT GEMMs
     // (callers that run many iterations pass them in, computed once)
@@ -558,88 +627,81 @@ std::vector<torch::Tensor> grouped_ff_bwd(
                         && (d % 64 == 0);
     torch::Tensor db1f;
     {
-        GemmParams p = base_params(M, m4, d, LAYOUT_NT, G, G, 1.0f);
-        p.A.base = (const char*)dY.data_ptr(); p.A.sin = d; p.A.ld = G * d;
-        p.B.base = w2t.data_ptr(); p.B.sin = m4 * d; p.B.ld = d;
-        p.Cbase = dHpre.data_ptr(); p.Csin = M * m4; p.Cld = m4;
+        GemmParams p = base_params(M, m4, d, LAYOUT_NT, Ga, Ga, 1.0f);
+        p.A.base = u16_at(dY, g_lo * d); p.A.sin = d; p.A.ld = G * d;
+        p.B.base = u16_at(w2t, g_lo * m4 * d); p.B.sin = m4 * d; p.B.ld = d;
+        p.Cbase = u16_at(dHpre, g_lo * M * m4); p.Csin = M * m4; p.Cld = m4;
         p.epilogue = EPI_GELUGRAD;
-        p.aux_base = Hpre.data_ptr(); p.aux_sin = M * m4; p.aux_ld = m4;
+        p.aux_base = u16_at(Hpre, g_lo * M * m4);
+        p.aux_sin = M * m4; p.aux_ld = m4;
         if (dh_nt3) {
             // per-64-row partials, fully written by the epilogue
-            db1f = torch::empty({G, M / 64, m4}, opts.dtype(at::kFloat));
+            db1f = torch::empty({Ga, M / 64, m4}, opts.dtype(at::kFloat));
             p.colsum_out = db1f.data_ptr<float>();
             p.colsum_sin = (M / 64) * m4;
         }
-        run_gemm(p, s, opts, true);
+        run_gemm(p, s, opts, true, G);
     }
     // dX_g = dHpre_g @ W1_g -- NT with W1^T, scattered into level slices
     {
-        GemmParams p = base_params(M, d, m4, LAYOUT_NT, G, G, 1.0f);
-        p.A.base = dHpre.data_ptr(); p.A.sin = M * m4; p.A.ld = m4;
-        p.B.base = w1t.data_ptr(); p.B.sin = d * m4; p.B.ld = m4;
+        GemmParams p = base_params(M, d, m4, LAYOUT_NT, Ga, Ga, 1.0f);
+        p.A.base = u16_at(dHpre, g_lo * M * m4); p.A.sin = M * m4; p.A.ld = m4;
+        p.B.base = u16_at(w1t, g_lo * d * m4); p.B.sin = d * m4; p.B.ld = m4;
         if (mode == 0) {
-            dTokens = torch::empty({B, N, d}, opts);
             p.Cflags = OP_TABLE;
-            p.Ctab[0] = dTokens.data_ptr();
-            p.Ctabld[0] = d;
-            for (int64_t g = 1; g < G; g++) {
-                p.Ctab[g] = (char*)dLevels.data_ptr() + (g - 1) * d * 2;
-                p.Ctabld[g] = L * d;
+            for (int64_t g = g_lo; g < G; g++) {
+                p.Ctab[g - g_lo] = g == 0 ? dTokens.data_ptr()
+                                          : u16_at(dLevels, (g - 1) * d);
+                p.Ctabld[g - g_lo] = g == 0 ? d : L * d;
             }
         } else {
-            p.Cbase = (char*)dLevels.data_ptr() + d * 2;
+            p.Cbase = u16_at(dLevels, (g_lo + 1) * d);
             p.Csin = d; p.Cld = L * d;
         }
-        run_gemm(p, s, opts, true);
+        run_gemm(p, s, opts, true, G);
     }
     // dW1_g[h, j] = sum_m dHpre_g[m, h] * x_g[m, j]
-    auto dW1 = torch::empty({G * m4, d}, opts);
     {
-        GemmParams p = base_params(m4, d, M, LAYOUT_TN, G, G, 1.0f);
-        p.A.base = dHpre.data_ptr(); p.A.sin = M * m4; p.A.ld = m4;
+        GemmParams p = base_params(m4, d, M, LAYOUT_TN, Ga, Ga, 1.0f);
+        p.A.base = u16_at(dHpre, g_lo * M * m4); p.A.sin = M * m4; p.A.ld = m4;
         if (mode == 0) {
             auto tokens = tokens_opt.value();
             CHECK_IN(tokens);
             p.B.flags = OP_TABLE;
-            p.Btab[0] = tokens.data_ptr();
-            p.Btabld[0] = d;
-            for (int64_t g = 1; g < G; g++) {
-                p.Btab[g] = (const char*)levels.data_ptr() + (g - 1) * d * 2;
-                p.Btabld[g] = L * d;
+            for (int64_t g = g_lo; g < G; g++) {
+                p.Btab[g - g_lo] = g == 0 ? tokens.data_ptr()
+                                          : u16_at(levels, (g - 1) * d);
+                p.Btabld[g - g_lo] = g == 0 ? d : L * d;
             }
         } else {
-            p.B.base = td_in.data_ptr();
+            p.B.base = u16_at(td_in, g_lo * d);
             p.B.sin = d; p.B.ld = G * d;
         }
-        p.Cbase = dW1.data_ptr(); p.Csin = m4 * d; p.Cld = d;
-        run_gemm(p, s, opts, true);
+        p.Cbase = u16_at(dW1, g_lo * m4 * d); p.Csin = m4 * d; p.Cld = d;
+        run_gemm(p, s, opts, true, G);
     }
     // dW2_g[o, h] = sum_m dY_g[m, o] * Hact_g[m, h]
-    auto dW2 = torch::empty({G * d, m4}, opts);
     {
-        GemmParams p = base_params(d, m4, M, LAYOUT_TN, G, G, 1.0f);
-        p.A.base = (const char*)dY.data_ptr(); p.A.sin = d; p.A.ld = G * d;
-        p.B.base = Hact.data_ptr(); p.B.sin = M * m4; p.B.ld = m4;
-        p.Cbase = dW2.data_ptr(); p.Csin = d * m4; p.Cld = m4;
-        run_gemm(p, s, opts, true);
+        GemmParams p = base_params(d, m4, M, LAYOUT_TN, Ga, Ga, 1.0f);
+        p.A.base = u16_at(dY, g_lo * d); p.A.sin = d; p.A.ld = G * d;
+        p.B.base = u16_at(Hact, g_lo * M * m4); p.B.sin = M * m4; p.B.ld = m4;
+        p.Cbase = u16_at(dW2, g_lo * d * m4); p.Csin = d * m4; p.Cld = m4;
+        run_gemm(p, s, opts, true, G);
     }
-    torch::Tensor dB1;
     if (dh_nt3) {
-        dB1 = torch::empty({G * m4}, opts);
-        launch_colsum_fin(db1f.data_ptr<float>(), dB1.data_ptr(), (int)G,
-                          m4, (int)(M / 64), s);
+        launch_colsum_fin(db1f.data_ptr<float>(), u16_at(dB1, g_lo * m4),
+                          (int)Ga, m4, (int)(M / 64), s);
         check_launch();
     } else {
         // native deterministic column sum (replaces ATen .sum(1))
-        dB1 = torch::empty({G * m4}, opts);
-        auto ws = torch::empty({(long)G * colsum_rb(M) * m4},
+        auto ws = torch::empty({(long)Ga * colsum_rb(M) * m4},
                                opts.dtype(at::kFloat));
-        launch_colsum(dHpre.data_ptr(), ws.data_ptr<float>(),
-                      dB1.data_ptr(), (int)G, M, m4, s);
+        launch_colsum(u16_at(dHpre, g_lo * M * m4), ws.data_ptr<float>(),
+                      u16_at(dB1, g_lo * m4), (int)Ga, M, m4, s);
         check_launch();
     }
-    // dB2 = colsum over the M token rows of dY viewed as (M, G*d)
-    auto dB2 = torch::empty({G * d}, opts);
+    // dB2 = colsum over the M token rows of dY viewed as (M, G*d); the
+    // dead groups' columns of dY are zero and sum to zero
     {
         auto ws = torch::empty({(long)colsum_rb(M) * G * d},
                                opts.dtype(at::kFloat));
@@ -647,7 +709,6 @@ std::vector<torch::Tensor> grouped_ff_bwd(
                       1, M, G * d, s);
         check_launch();
     }
-    if (mode != 0) dTokens = torch::empty({0}, opts);
     return {dTokens, dLevels, dW1, dB1, dW2, dB2};
 }
 
@@ -733,19 +794,38 @@ std::vector<torch::Tensor> consensus_fwd(
     return {out, probs, rnorm};
 }
 
+// `l_lo` (level cone): dOut is zero in levels < l_lo, so is the result
+// there; the GEMMs and the combine run on levels [l_lo, L) of every batch
+// entry. Every per-level buffer keeps all L levels and is entered at level
+// l_lo (base + l_lo * inner stride, nInner = L - l_lo).
 torch::Tensor consensus_bwd(torch::Tensor dOut, torch::Tensor levels,
                             torch::Tensor probs, torch::Tensor rnorm,
                             bool attend_self,
-                            c10::optional<torch::Tensor> mask_opt) {
+                            c10::optional<torch::Tensor> mask_opt,
+                            int64_t l_lo = 0) {
     CHECK_IN(dOut); CHECK_IN(levels); CHECK_IN(probs);
     const int64_t B = levels.size(0), N = levels.size(1),
                   L = levels.size(2), d = levels.size(3);
-    const int64_t P = B * L;
+    TORCH_CHECK(l_lo >= 0 && l_lo <= L, "l_lo out of range");
+    const int64_t Ll = L - l_lo;
+    const int64_t P = B * Ll;       // live problems
+    const int64_t Pfull = B * L;    // what the dispatch gates are judged by
     const bool lds_ok = (N % 8 == 0) && (d % 8 == 0);
     auto opts = levels.options();
     hipStream_t s = cur_stream();
     const bool* mask = nullptr;
     if (mask_opt.has_value()) mask = mask_opt.value().data_ptr<bool>();
+
+    auto dLevels = torch::empty({B, N, L, d}, opts);
+    launch_zero_slices(dLevels.data_ptr(), B * N, (int)L, (int)d, 0,
+                       (int)l_lo, s);
+    check_launch();
+    if (Ll == 0) return dLevels;
+    TORCH_CHECK(l_lo == 0 || d % 8 == 0, "l_lo needs dim % 8 == 0");
+    const float* rn = rnorm.data_ptr<float>();
+    // level l_lo of a (B,N,L,d) / (B,L,N,N) / (B,L,N,d) bf16 buffer
+    auto lv = [&](const torch::Tensor& t) { return u16_at(t, l_lo * d); };
+    auto nn = [&](const torch::Tensor& t) { return u16_at(t, l_lo * N * N); };
 
     // dP[i,j] = dOut_i . v_j, then row softmax backward -> dS, dSr
     const bool fused_sm = (N == 256) && (d % 64 == 0) && lds_ok;
@@ -753,19 +833,19 @@ torch::Tensor consensus_bwd(torch::Tensor dOut, torch::Tensor levels,
     auto dSr = torch::empty({B, L, N, N}, opts);
     torch::Tensor dP;
     if (fused_sm) {
-        GemmParams p = base_params(N, N, d, LAYOUT_NT, P, L, 1.0f);
-        p.A.base = dOut.data_ptr(); p.A.sin = d; p.A.sout = N * L * d;
+        GemmParams p = base_params(N, N, d, LAYOUT_NT, P, Ll, 1.0f);
+        p.A.base = lv(dOut); p.A.sin = d; p.A.sout = N * L * d;
         p.A.ld = L * d;
-        p.B.base = levels.data_ptr(); p.B.sin = d; p.B.sout = N * L * d;
+        p.B.base = lv(levels); p.B.sin = d; p.B.sout = N * L * d;
         p.B.ld = L * d;
-        p.Cbase = dS.data_ptr(); p.Csin = N * N; p.Csout = L * N * N;
+        p.Cbase = nn(dS); p.Csin = N * N; p.Csout = L * N * N;
         p.Cld = N;
         p.epilogue = EPI_SMBWD;
-        p.aux_base = probs.data_ptr();
+        p.aux_base = nn(probs);
         p.aux_sin = N * N; p.aux_sout = L * N * N; p.aux_ld = N;
-        p.out2 = dSr.data_ptr();
+        p.out2 = nn(dSr);
         p.out2_sin = N * N; p.out2_sout = L * N * N; p.out2_ld = N;
-        p.colscale_base = rnorm.data_ptr<float>();
+        p.colscale_base = rn + l_lo * N;
         p.cs_sin = N; p.cs_sout = L * N; p.has_colscale = 1;
         p.self_mask = attend_self ? 0 : 1;
         p.nlmask = mask;
@@ -775,63 +855,62 @@ torch::Tensor consensus_bwd(torch::Tensor dOut, torch::Tensor levels,
         check_launch();
     } else {
         dP = torch::empty({B, L, N, N}, opts);
-        GemmParams p = base_params(N, N, d, LAYOUT_NT, P, L, 1.0f);
-        p.A.base = dOut.data_ptr(); p.A.sin = d; p.A.sout = N * L * d;
+        GemmParams p = base_params(N, N, d, LAYOUT_NT, P, Ll, 1.0f);
+        p.A.base = lv(dOut); p.A.sin = d; p.A.sout = N * L * d;
         p.A.ld = L * d;
-        p.B.base = levels.data_ptr(); p.B.sin = d; p.B.sout = N * L * d;
+        p.B.base = lv(levels); p.B.sin = d; p.B.sout = N * L * d;
         p.B.ld = L * d;
-        p.Cbase = dP.data_ptr(); p.Csin = N * N; p.Csout = L * N * N;
+        p.Cbase = nn(dP); p.Csin = N * N; p.Csout = L * N * N;
         p.Cld = N;
-        run_gemm(p, s, opts, lds_ok);
-        launch_softmax_bwd(probs.data_ptr(), dP.data_ptr(),
-                           rnorm.data_ptr<float>(), dS.data_ptr(),
-                           dSr.data_ptr(), mask, (int)P, (int)N,
-                           attend_self ? 0 : 1,
-                           (float)std::pow((double)d, -0.5), s);
+        run_gemm(p, s, opts, lds_ok, Pfull);
+        launch_softmax_bwd(probs.data_ptr(), dP.data_ptr(), rn,
+                           dS.data_ptr(), dSr.data_ptr(), mask, (int)P,
+                           (int)N, attend_self ? 0 : 1,
+                           (float)std::pow((double)d, -0.5), s, (int)L,
+                           (int)l_lo);
         check_launch();
     }
 
     // dv[j,:] = sum_i P[i,j] dOut[i,:]
     auto dv = torch::empty({B, N, L, d}, opts);
     {
-        GemmParams p = base_params(N, d, N, LAYOUT_TN, P, L, 1.0f);
-        p.A.base = probs.data_ptr(); p.A.sin = N * N; p.A.sout = L * N * N;
+        GemmParams p = base_params(N, d, N, LAYOUT_TN, P, Ll, 1.0f);
+        p.A.base = nn(probs); p.A.sin = N * N; p.A.sout = L * N * N;
         p.A.ld = N;
-        p.B.base = dOut.data_ptr(); p.B.sin = d; p.B.sout = N * L * d;
+        p.B.base = lv(dOut); p.B.sin = d; p.B.sout = N * L * d;
         p.B.ld = L * d;
-        p.Cbase = dv.data_ptr(); p.Csin = d; p.Csout = N * L * d;
+        p.Cbase = lv(dv); p.Csin = d; p.Csout = N * L * d;
         p.Cld = L * d;
-        run_gemm(p, s, opts, lds_ok);
+        run_gemm(p, s, opts, lds_ok, Pfull);
     }
     // dq[i,:] = sum_j dSr[i,j] levels[j,:]
     auto dq = torch::empty({B, N, L, d}, opts);
     {
-        GemmParams p = base_params(N, d, N, LAYOUT_NN, P, L, 1.0f);
-        p.A.base = dSr.data_ptr(); p.A.sin = N * N; p.A.sout = L * N * N;
+        GemmParams p = base_params(N, d, N, LAYOUT_NN, P, Ll, 1.0f);
+        p.A.base = nn(dSr); p.A.sin = N * N; p.A.sout = L * N * N;
         p.A.ld = N;
-        p.B.base = levels.data_ptr(); p.B.sin = d; p.B.sout = N * L * d;
+        p.B.base = lv(levels); p.B.sin = d; p.B.sout = N * L * d;
         p.B.ld = L * d;
-        p.Cbase = dq.data_ptr(); p.Csin = d; p.Csout = N * L * d;
+        p.Cbase = lv(dq); p.Csin = d; p.Csout = N * L * d;
         p.Cld = L * d;
-        run_gemm(p, s, opts, lds_ok);
+        run_gemm(p, s, opts, lds_ok, Pfull);
     }
     // dkhat[j,:] = sum_i dS[i,j] levels[i,:]   (layout (B,L,N,d))
     auto dkhat = torch::empty({B, L, N, d}, opts);
     {
-        GemmParams p = base_params(N, d, N, LAYOUT_TN, P, L, 1.0f);
-        p.A.base = dS.data_ptr(); p.A.sin = N * N; p.A.sout = L * N * N;
+        GemmParams p = base_params(N, d, N, LAYOUT_TN, P, Ll, 1.0f);
+        p.A.base = nn(dS); p.A.sin = N * N; p.A.sout = L * N * N;
         p.A.ld = N;
-        p.B.base = levels.data_ptr(); p.B.sin = d; p.B.sout = N * L * d;
+        p.B.base = lv(levels); p.B.sin = d; p.B.sout = N * L * d;
         p.B.ld = L * d;
-        p.Cbase = dkhat.data_ptr(); p.Csin = N * d; p.Csout = L * N * d;
+        p.Cbase = u16_at(dkhat, l_lo * N * d);
+        p.Csin = N * d; p.Csout = L * N * d;
         p.Cld = d;
-        run_gemm(p, s, opts, lds_ok);
+        run_gemm(p, s, opts, lds_ok, Pfull);
     }
-    auto dLevels = torch::empty({B, N, L, d}, opts);
-    launch_knorm_combine(dkhat.data_ptr(), levels.data_ptr(),
-                         rnorm.data_ptr<float>(), dv.data_ptr(),
-                         dq.data_ptr(), dLevels.data_ptr(),
-                         (int)B, (int)N, (int)L, (int)d, s);
+    launch_knorm_combine(dkhat.data_ptr(), levels.data_ptr(), rn,
+                         dv.data_ptr(), dq.data_ptr(), dLevels.data_ptr(),
+                         (int)B, (int)N, (int)L, (int)d, s, (int)l_lo);
     check_launch();
     return dLevels;
 }
@@ -916,15 +995,23 @@ std::vector<torch::Tensor> glom_step_bwd(
         c10::optional<torch::Tensor> bw1t, c10::optional<torch::Tensor> bw2t,
         c10::optional<torch::Tensor> tw1t,
         c10::optional<torch::Tensor> tw2t,
-        c10::optional<torch::Tensor> td_in = c10::nullopt) {
+        c10::optional<torch::Tensor> td_in = c10::nullopt,
+        int64_t lo = 0) {
+    // lo (level cone): dnew is zero in levels < lo. dmix / dtd inherit the
+    // zeros; bottom-up groups, top-down groups and consensus levels below
+    // lo are skipped and their (zero) results filled in, so add4 and dpos
+    // below read what the full computation would have produced
     const int64_t L = levels.size(2);
+    TORCH_CHECK(lo >= 0 && lo < L, "lo out of range");
     auto mix = level_mix_bwd(dnew);        // {dmix, dtd}
     auto bu = grouped_ff_bwd(mix[0], tokens, levels, c10::nullopt, bw1,
-                             bw2, buHpre, buHact, 0, bw1t, bw2t);
+                             bw2, buHpre, buHact, 0, bw1t, bw2t,
+                             c10::nullopt, lo);
     auto td = grouped_ff_bwd(mix[1], c10::nullopt, levels, pos, tw1, tw2,
-                             tdHpre, tdHact, 1, tw1t, tw2t, td_in);
+                             tdHpre, tdHact, 1, tw1t, tw2t, td_in,
+                             std::min<int64_t>(lo, L - 1));
     auto dAttn = consensus_bwd(mix[0], levels, probs, rnorm, attend_self,
-                               mask);
+                               mask, lo);
     auto dLevels = torch::empty_like(levels);
     launch_add4(mix[0].data_ptr(), bu[1].data_ptr(), td[1].data_ptr(),
                 dAttn.data_ptr(), dLevels.data_ptr(), levels.numel(),
@@ -1029,42 +1116,49 @@ void add4_into(torch::Tensor a, torch::Tensor b, torch::Tensor c,
 // Fine-grained FF backward stages (stream-forked by the python layer):
 // dH (with fused dB1), then dX and dW independently.
 
+// The three stages take the first live group `g_lo` like grouped_ff_bwd
+// (level cone): dHpre keeps its (G, M, m4) shape, its dead groups are
+// neither written here nor read by the two stages after it.
 std::vector<torch::Tensor> ff_bwd_dh(torch::Tensor dY, torch::Tensor w2t,
-                                     torch::Tensor Hpre) {
+                                     torch::Tensor Hpre, int64_t g_lo = 0) {
     CHECK_IN(dY); CHECK_IN(w2t); CHECK_IN(Hpre);
+    TORCH_CHECK(Hpre.dim() == 3, "Hpre must be (G, M, m4)");
     const int64_t G = Hpre.size(0), M = Hpre.size(1), m4 = Hpre.size(2);
     const int64_t d = dY.size(3);
+    TORCH_CHECK(g_lo >= 0 && g_lo <= G, "g_lo out of range");
+    const int64_t Ga = G - g_lo;
     auto opts = dY.options();
     hipStream_t s = cur_stream();
     auto dHpre = torch::empty({G, M, m4}, opts);
+    auto dB1 = torch::empty({G * m4}, opts);
+    zero_fill(dB1.data_ptr(), g_lo * m4 * 2, s);
+    if (Ga == 0) return {dHpre, dB1};
     const bool fused = (M % 128 == 0) && (m4 % 256 == 0) && (m4 >= 1024)
                        && (d % 64 == 0);
     torch::Tensor db1f;
-    GemmParams p = base_params(M, m4, d, LAYOUT_NT, G, G, 1.0f);
-    p.A.base = (const char*)dY.data_ptr(); p.A.sin = d; p.A.ld = G * d;
-    p.B.base = w2t.data_ptr(); p.B.sin = m4 * d; p.B.ld = d;
-    p.Cbase = dHpre.data_ptr(); p.Csin = M * m4; p.Cld = m4;
+    GemmParams p = base_params(M, m4, d, LAYOUT_NT, Ga, Ga, 1.0f);
+    p.A.base = u16_at(dY, g_lo * d); p.A.sin = d; p.A.ld = G * d;
+    p.B.base = u16_at(w2t, g_lo * m4 * d); p.B.sin = m4 * d; p.B.ld = d;
+    p.Cbase = u16_at(dHpre, g_lo * M * m4); p.Csin = M * m4; p.Cld = m4;
     p.epilogue = EPI_GELUGRAD;
-    p.aux_base = Hpre.data_ptr(); p.aux_sin = M * m4; p.aux_ld = m4;
+    p.aux_base = u16_at(Hpre, g_lo * M * m4);
+    p.aux_sin = M * m4; p.aux_ld = m4;
     if (fused) {
         // per-64-row partials, fully written by the epilogue
-        db1f = torch::empty({G, M / 64, m4}, opts.dtype(at::kFloat));
+        db1f = torch::empty({Ga, M / 64, m4}, opts.dtype(at::kFloat));
         p.colsum_out = db1f.data_ptr<float>();
         p.colsum_sin = (M / 64) * m4;
     }
-    run_gemm(p, s, opts, true);
-    torch::Tensor dB1;
+    run_gemm(p, s, opts, true, G);
     if (fused) {
-        dB1 = torch::empty({G * m4}, opts);
-        launch_colsum_fin(db1f.data_ptr<float>(), dB1.data_ptr(), (int)G,
-                          m4, (int)(M / 64), s);
+        launch_colsum_fin(db1f.data_ptr<float>(), u16_at(dB1, g_lo * m4),
+                          (int)Ga, m4, (int)(M / 64), s);
         check_launch();
     } else {
-        dB1 = torch::empty({G * m4}, opts);
-        auto cws = torch::empty({(long)G * colsum_rb(M) * m4},
+        auto cws = torch::empty({(long)Ga * colsum_rb(M) * m4},
                                 opts.dtype(at::kFloat));
-        launch_colsum(dHpre.data_ptr(), cws.data_ptr<float>(),
-                      dB1.data_ptr(), (int)G, M, m4, s);
+        launch_colsum(u16_at(dHpre, g_lo * M * m4), cws.data_ptr<float>(),
+                      u16_at(dB1, g_lo * m4), (int)Ga, M, m4, s);
         check_launch();
     }
     return {dHpre, dB1};
@@ -1073,37 +1167,43 @@ std::vector<torch::Tensor> ff_bwd_dh(torch::Tensor dY, torch::Tensor w2t,
 std::vector<torch::Tensor> ff_bwd_dx(torch::Tensor dHpre, torch::Tensor w1t,
                                      c10::optional<torch::Tensor> tokens_opt,
                                      int64_t B, int64_t N, int64_t L,
-                                     int64_t mode) {
+                                     int64_t mode, int64_t g_lo = 0) {
     CHECK_IN(dHpre); CHECK_IN(w1t);
     const int64_t G = dHpre.size(0), M = dHpre.size(1), m4 = dHpre.size(2);
     const int64_t d = w1t.numel() / (G * m4);
+    TORCH_CHECK(g_lo >= 0 && g_lo <= G, "g_lo out of range");
+    TORCH_CHECK(G == (mode == 0 ? L : L - 1) && M == B * N,
+                "dHpre does not match (B, N, L)");
+    const int64_t Ga = G - g_lo;
     auto opts = dHpre.options();
     hipStream_t s = cur_stream();
     torch::Tensor dTokens;
     auto dLevels = torch::empty({B, N, L, d}, opts);
-    launch_zero_slice(dLevels.data_ptr(), B * N, (int)L, (int)d,
-                      mode == 0 ? (int)L - 1 : 0, s);
-    check_launch();
-    GemmParams p = base_params(M, d, m4, LAYOUT_NT, G, G, 1.0f);
-    p.A.base = dHpre.data_ptr(); p.A.sin = M * m4; p.A.ld = m4;
-    p.B.base = w1t.data_ptr(); p.B.sin = d * m4; p.B.ld = m4;
+    zero_unwritten_dx(dLevels.data_ptr(), B * N, L, d, mode, g_lo, s);
     if (mode == 0) {
         auto tokens = tokens_opt.value();
         CHECK_IN(tokens);
         dTokens = torch::empty({B, N, d}, opts);
+        if (g_lo > 0) zero_fill(dTokens.data_ptr(), M * d * 2, s);
+    } else {
+        dTokens = torch::empty({0}, opts);
+    }
+    if (Ga == 0) return {dTokens, dLevels};
+    GemmParams p = base_params(M, d, m4, LAYOUT_NT, Ga, Ga, 1.0f);
+    p.A.base = u16_at(dHpre, g_lo * M * m4); p.A.sin = M * m4; p.A.ld = m4;
+    p.B.base = u16_at(w1t, g_lo * d * m4); p.B.sin = d * m4; p.B.ld = m4;
+    if (mode == 0) {
         p.Cflags = OP_TABLE;
-        p.Ctab[0] = dTokens.data_ptr();
-        p.Ctabld[0] = d;
-        for (int64_t g = 1; g < G; g++) {
-            p.Ctab[g] = (char*)dLevels.data_ptr() + (g - 1) * d * 2;
-            p.Ctabld[g] = L * d;
+        for (int64_t g = g_lo; g < G; g++) {
+            p.Ctab[g - g_lo] = g == 0 ? dTokens.data_ptr()
+                                      : u16_at(dLevels, (g - 1) * d);
+            p.Ctabld[g - g_lo] = g == 0 ? d : L * d;
         }
     } else {
-        p.Cbase = (char*)dLevels.data_ptr() + d * 2;
+        p.Cbase = u16_at(dLevels, (g_lo + 1) * d);
         p.Csin = d; p.Cld = L * d;
     }
-    run_gemm(p, s, opts, true);
-    if (mode != 0) dTokens = torch::empty({0}, opts);
+    run_gemm(p, s, opts, true, G);
     return {dTokens, dLevels};
 }
 
@@ -1112,13 +1212,27 @@ std::vector<torch::Tensor> ff_bwd_dw(
         c10::optional<torch::Tensor> tokens_opt, torch::Tensor levels,
         c10::optional<torch::Tensor> pos_opt, torch::Tensor Hact,
         int64_t mode,
-        c10::optional<torch::Tensor> td_in_opt = c10::nullopt) {
+        c10::optional<torch::Tensor> td_in_opt = c10::nullopt,
+        int64_t g_lo = 0) {
     CHECK_IN(dY); CHECK_IN(dHpre); CHECK_IN(levels); CHECK_IN(Hact);
     const int64_t B = levels.size(0), N = levels.size(1),
                   L = levels.size(2), d = levels.size(3);
     const int64_t G = dHpre.size(0), M = dHpre.size(1), m4 = dHpre.size(2);
+    TORCH_CHECK(g_lo >= 0 && g_lo <= G, "g_lo out of range");
+    TORCH_CHECK(G == (mode == 0 ? L : L - 1) && M == B * N,
+                "dHpre does not match levels");
+    const int64_t Ga = G - g_lo;
     auto opts = levels.options();
     hipStream_t s = cur_stream();
+    auto dW1 = torch::empty({G * m4, d}, opts);
+    auto dW2 = torch::empty({G * d, m4}, opts);
+    auto dB2 = torch::empty({G * d}, opts);
+    zero_fill(dW1.data_ptr(), g_lo * m4 * d * 2, s);
+    zero_fill(dW2.data_ptr(), g_lo * d * m4 * 2, s);
+    if (Ga == 0) {
+        zero_fill(dB2.data_ptr(), G * d * 2, s);
+        return {dW1, dW2, dB2};
+    }
     torch::Tensor td_in;
     if (mode == 1) {
         if (td_in_opt.has_value() && td_in_opt->numel() > 0) {
@@ -1133,36 +1247,35 @@ std::vector<torch::Tensor> ff_bwd_dw(
             check_launch();
         }
     }
-    auto dW1 = torch::empty({G * m4, d}, opts);
     {
-        GemmParams p = base_params(m4, d, M, LAYOUT_TN, G, G, 1.0f);
-        p.A.base = dHpre.data_ptr(); p.A.sin = M * m4; p.A.ld = m4;
+        GemmParams p = base_params(m4, d, M, LAYOUT_TN, Ga, Ga, 1.0f);
+        p.A.base = u16_at(dHpre, g_lo * M * m4);
+        p.A.sin = M * m4; p.A.ld = m4;
         if (mode == 0) {
             auto tokens = tokens_opt.value();
             CHECK_IN(tokens);
             p.B.flags = OP_TABLE;
-            p.Btab[0] = tokens.data_ptr();
-            p.Btabld[0] = d;
-            for (int64_t g = 1; g < G; g++) {
-                p.Btab[g] = (const char*)levels.data_ptr() + (g - 1) * d * 2;
-                p.Btabld[g] = L * d;
+            for (int64_t g = g_lo; g < G; g++) {
+                p.Btab[g - g_lo] = g == 0 ? tokens.data_ptr()
+                                          : u16_at(levels, (g - 1) * d);
+                p.Btabld[g - g_lo] = g == 0 ? d : L * d;
             }
         } else {
-            p.B.base = td_in.data_ptr();
+            p.B.base = u16_at(td_in, g_lo * d);
             p.B.sin = d; p.B.ld = G * d;
         }
-        p.Cbase = dW1.data_ptr(); p.Csin = m4 * d; p.Cld = d;
-        run_gemm(p, s, opts, true);
+        p.Cbase = u16_at(dW1, g_lo * m4 * d); p.Csin = m4 * d; p.Cld = d;
+        run_gemm(p, s, opts, true, G);
     }
-    auto dW2 = torch::empty({G * d, m4}, opts);
     {
-        GemmParams p = base_params(d, m4, M, LAYOUT_TN, G, G, 1.0f);
-        p.A.base = (const char*)dY.data_ptr(); p.A.sin = d; p.A.ld = G * d;
-        p.B.base = Hact.data_ptr(); p.B.sin = M * m4; p.B.ld = m4;
-        p.Cbase = dW2.data_ptr(); p.Csin = d * m4; p.Cld = m4;
-        run_gemm(p, s, opts, true);
+        GemmParams p = base_params(d, m4, M, LAYOUT_TN, Ga, Ga, 1.0f);
+        p.A.base = u16_at(dY, g_lo * d); p.A.sin = d; p.A.ld = G * d;
+        p.B.base = u16_at(Hact, g_lo * M * m4);
+        p.B.sin = M * m4; p.B.ld = m4;
+        p.Cbase = u16_at(dW2, g_lo * d * m4); p.Csin = d * m4; p.Cld = m4;
+        run_gemm(p, s, opts, true, G);
     }
-    auto dB2 = torch::empty({G * d}, opts);
+    // the dead groups' columns of dY are zero and sum to zero
     {
         auto cws = torch::empty({(long)colsum_rb(M) * G * d},
                                 opts.dtype(at::kFloat));
@@ -1629,9 +1742,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("Hpre"), py::arg("Hact"), py::arg("mode"),
           py::arg("w1t") = c10::nullopt,
           py::arg("w2t") = c10::nullopt,
-          py::arg("td_in") = c10::nullopt);
+          py::arg("td_in") = c10::nullopt, py::arg("g_lo") = 0);
     m.def("consensus_fwd", &consensus_fwd, "consensus attention forward");
-    m.def("consensus_bwd", &consensus_bwd, "consensus attention backward");
+    m.def("consensus_bwd", &consensus_bwd, "consensus attention backward",
+          py::arg("dOut"), py::arg("levels"), py::arg("probs"),
+          py::arg("rnorm"), py::arg("attend_self"), py::arg("mask"),
+          py::arg("l_lo") = 0);
     m.def("level_mix_fwd", &level_mix_fwd, "level mix forward",
           py::arg("levels"), py::arg("bu"), py::arg("td"), py::arg("cons"),
           py::arg("slab") = c10::nullopt, py::arg("slab_idx") = 0);
@@ -1651,7 +1767,7 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("rnorm"), py::arg("attend_self"), py::arg("mask"),
           py::arg("bw1t") = c10::nullopt, py::arg("bw2t") = c10::nullopt,
           py::arg("tw1t") = c10::nullopt, py::arg("tw2t") = c10::nullopt,
-          py::arg("td_in") = c10::nullopt);
+          py::arg("td_in") = c10::nullopt, py::arg("lo") = 0);
     m.def("patch_embed_fwd", &patch_embed_fwd,
           "patchify + embed GEMM (K1)");
     m.def("patch_embed_bwd", &patch_embed_bwd, "patch embed backward");
@@ -1660,12 +1776,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("fused_adamw", &fused_adamw,
           "fused AdamW + global-norm grad clip (torch semantics)");
     m.def("add4_into", &add4_into, "fused 4-way elementwise sum");
-    m.def("ff_bwd_dh", &ff_bwd_dh);
-    m.def("ff_bwd_dx", &ff_bwd_dx);
+    m.def("ff_bwd_dh", &ff_bwd_dh, py::arg("dY"), py::arg("w2t"),
+          py::arg("Hpre"), py::arg("g_lo") = 0);
+    m.def("ff_bwd_dx", &ff_bwd_dx, py::arg("dHpre"), py::arg("w1t"),
+          py::arg("tokens"), py::arg("B"), py::arg("N"), py::arg("L"),
+          py::arg("mode"), py::arg("g_lo") = 0);
     m.def("ff_bwd_dw", &ff_bwd_dw, py::arg("dY"), py::arg("dHpre"),
           py::arg("tokens"), py::arg("levels"), py::arg("pos"),
           py::arg("Hact"), py::arg("mode"),
-          py::arg("td_in") = c10::nullopt);
+          py::arg("td_in") = c10::nullopt, py::arg("g_lo") = 0);
     m.def("set_nt8p", &set_nt8p, "toggle the 8-phase NT kernel (A/B)");
     m.def("set_tn_tr", &set_tn_tr,
           "toggle the transposed-read TN kernel (A/B, same bits)");

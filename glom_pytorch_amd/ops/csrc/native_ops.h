@@ -30,6 +30,9 @@ void launch_dpos(const void* dlev, void* out, float* partials, int BCH,
 // zero the single level slice out[:, :, l0, :] of a (B,N,L,d) tensor
 void launch_zero_slice(void* out, long BN, int L, int d, int l0,
                        hipStream_t s);
+// zero the level slices out[:, :, l0 : l0 + nl, :]; nl <= 0 launches nothing
+void launch_zero_slices(void* out, long BN, int L, int d, int l0, int nl,
+                        hipStream_t s);
 
 // ---------------- fused AdamW ----------------
 #define OPT_MAX_T 24

@@ -305,6 +305,27 @@ void launch_zero_slice(void* out, long BN, int L, int d, int l0,
                        dim3(NT256), 0, s, (ushort_t*)out, BN, L, d, l0);
 }
 
+// the run of nl adjacent slices out[bn, l0 : l0 + nl, :] = 0: per bn row a
+// contiguous span of w = nl * d elements (d % 8 == 0)
+__global__ __launch_bounds__(NT256) void k_zero_slices(
+        ushort_t* __restrict__ out, long BN, long Ld, long w, long off) {
+    long i8 = ((long)blockIdx.x * NT256 + threadIdx.x) * 8;
+    if (i8 >= BN * w) return;
+    long q = i8 % w;
+    long bn = i8 / w;
+    uint4v z = {0, 0, 0, 0};
+    *(uint4v*)(out + bn * Ld + off + q) = z;
+}
+
+void launch_zero_slices(void* out, long BN, int L, int d, int l0, int nl,
+                        hipStream_t s) {
+    if (nl <= 0 || BN <= 0) return;
+    const long w = (long)nl * d;
+    hipLaunchKernelGGL(k_zero_slices, dim3(cdivl(BN * w / 8, NT256)),
+                       dim3(NT256), 0, s, (ushort_t*)out, BN, (long)L * d, w,
+                       (long)l0 * d);
+}
+
 // --------------------------------------------------------------------- //
 // fused AdamW
 

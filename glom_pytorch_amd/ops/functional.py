@@ -212,14 +212,21 @@ class GlomStepFn(torch.autograd.Function):
     def forward(ctx, tokens, levels, pos, bw1, bb1, bw2, bb2,
                 tw1, tb1, tw2, tb2, attend_self, mask,
                 bw1t, bw2t, tw1t, tw2t, slab_ref=None,
-                save_for_bwd=True):
+                save_for_bwd=True, cone=None):
         # slab_ref: optional (slab, idx) — write the step output straight
         # into the preallocated trajectory slab (untracked alias return)
         # save_for_bwd: False on forward-only steps (decided by glom_step,
         # outside this Function) — the FF pre-activations, which only the
         # backward reads, are then neither allocated nor written
+        # cone: None, or (lo, t) — glom_forward's promise that the gradient
+        # arriving at this step (iteration t) is zero in levels < lo. The
+        # backward then runs the groups / levels >= lo only. With lo = L-1
+        # no top-down group is live, so its pre-activations are not kept
         ext = _load_extension()
         slab, sidx = slab_ref if slab_ref is not None else (None, 0)
+        lo = cone[0] if cone is not None else 0
+        save_td = save_for_bwd and (lo < levels.size(2) - 1
+                                    or FORCE_SAVE_FOR_BWD)
         if (torch.is_grad_enabled()
                 and os.environ.get("GLOM_FWD_STREAMS", "0") != "1"):
             # never taken: grad mode is always disabled inside a custom
@@ -246,7 +253,7 @@ class GlomStepFn(torch.autograd.Function):
                 tdY, thp, tha, tdin = ext.grouped_ff_fwd(None, levels, pos,
                                                          tw1, tb1, tw2,
                                                          tb2, 1,
-                                                         save_for_bwd)
+                                                         save_td)
             with torch.cuda.stream(s_at):
                 s_at.wait_event(ev)
                 cons, probs, rnorm = ext.consensus_fwd(levels, attend_self,
@@ -263,6 +270,7 @@ class GlomStepFn(torch.autograd.Function):
                               bhp, bha, thp, tha, probs, rnorm, mask,
                               bw1t, bw2t, tw1t, tw2t, tdin)
         ctx.attend_self = attend_self
+        ctx.cone = cone
         return out
 
     @staticmethod
@@ -271,15 +279,24 @@ class GlomStepFn(torch.autograd.Function):
         (tokens, levels, pos, bw1, bw2, tw1, tw2, bhp, bha, thp, tha,
          probs, rnorm, mask, bw1t, bw2t, tw1t, tw2t,
          tdin) = ctx.saved_tensors
+        # level cone: groups / levels below lo carry an exactly-zero
+        # gradient; the ops skip them and fill in the zeros. The top-down
+        # MLP has groups 0..L-2: with lo = L-1 none is live (td_live)
+        L = levels.size(2)
+        lo = ctx.cone[0] if ctx.cone is not None else 0
+        if lo > 0 and CHECK_LEVEL_CONE:
+            _check_cone(dnew, lo, ctx.cone[1])
+        td_lo = min(lo, L - 1)
+        td_live = td_lo < L - 1
         if os.environ.get("GLOM_NO_BWD_STREAMS", "0") == "1":
             (dTokens, dLevels, dPos, dbw1, dbb1, dbw2, dbb2,
              dtw1, dtb1, dtw2, dtb2) = ext.glom_step_bwd(
                 dnew.contiguous(), tokens, levels, pos, bw1, bw2, tw1, tw2,
                 bhp, bha, thp, tha, probs, rnorm, ctx.attend_self, mask,
-                bw1t, bw2t, tw1t, tw2t, tdin)
+                bw1t, bw2t, tw1t, tw2t, tdin, lo)
             return (dTokens, dLevels, dPos, dbw1, dbb1, dbw2, dbb2,
                     dtw1, dtb1, dtw2, dtb2, None, None, None, None, None,
-                    None, None, None)
+                    None, None, None, None)
         if os.environ.get("GLOM_BWD_FORK", "3") == "3":
             cur = torch.cuda.current_stream()
             s_td, s_at, _ = GlomStepFn._side_streams()
@@ -287,20 +304,28 @@ class GlomStepFn(torch.autograd.Function):
             ev = torch.cuda.Event()
             ev.record(cur)
             bu = ext.grouped_ff_bwd(dmix, tokens, levels, None, bw1, bw2,
-                                    bhp, bha, 0, bw1t, bw2t)
-            with torch.cuda.stream(s_td):
-                s_td.wait_event(ev)
+                                    bhp, bha, 0, bw1t, bw2t, None, lo)
+            if td_live:
+                with torch.cuda.stream(s_td):
+                    s_td.wait_event(ev)
+                    td = ext.grouped_ff_bwd(dtd, None, levels, pos, tw1,
+                                            tw2, thp, tha, 1, tw1t, tw2t,
+                                            tdin, td_lo)
+                dtd.record_stream(s_td)
+            else:
+                # no live top-down group: only zero fills, no side stream
                 td = ext.grouped_ff_bwd(dtd, None, levels, pos, tw1, tw2,
-                                        thp, tha, 1, tw1t, tw2t, tdin)
+                                        thp, tha, 1, tw1t, tw2t, tdin,
+                                        td_lo)
             with torch.cuda.stream(s_at):
                 s_at.wait_event(ev)
                 dAttn = ext.consensus_bwd(dmix, levels, probs, rnorm,
-                                          ctx.attend_self, mask)
+                                          ctx.attend_self, mask, lo)
             dmix.record_stream(s_at)
-            dtd.record_stream(s_td)
-            cur.wait_stream(s_td)
+            if td_live:
+                cur.wait_stream(s_td)
             cur.wait_stream(s_at)
-            for t in list(td) + [dAttn]:
+            for t in (list(td) if td_live else []) + [dAttn]:
                 if t is not None and t.numel():
                     t.record_stream(cur)
             dLevels = torch.empty_like(levels)
@@ -308,54 +333,71 @@ class GlomStepFn(torch.autograd.Function):
             dPos = ext.dpos(td[1])
             return (bu[0], dLevels, dPos, bu[2], bu[3], bu[4], bu[5],
                     td[2], td[3], td[4], td[5], None, None, None, None,
-                    None, None, None, None)
+                    None, None, None, None, None)
         # 4-way fork variant (weight grads on a dedicated stream): measured
         # slightly SLOWER than the 3-way fork above (sync overhead), kept
         # behind GLOM_BWD_FORK=4 for future tuning.
-        B, N, L = levels.size(0), levels.size(1), levels.size(2)
+        B, N = levels.size(0), levels.size(1)
         cur = torch.cuda.current_stream()
         s_td, s_at, s_w = GlomStepFn._side_streams()
         dmix, dtd = ext.level_mix_bwd(dnew.contiguous())
         ev0 = torch.cuda.Event()
         ev0.record(cur)
-        bu_dh, bu_db1 = ext.ff_bwd_dh(dmix, bw2t, bhp)
+        bu_dh, bu_db1 = ext.ff_bwd_dh(dmix, bw2t, bhp, lo)
         ev_bu = torch.cuda.Event()
         ev_bu.record(cur)
-        with torch.cuda.stream(s_td):
-            s_td.wait_event(ev0)
-            td_dh, td_db1 = ext.ff_bwd_dh(dtd, tw2t, thp)
-            ev_td = torch.cuda.Event()
-            ev_td.record(s_td)
+        if td_live:
+            with torch.cuda.stream(s_td):
+                s_td.wait_event(ev0)
+                td_dh, td_db1 = ext.ff_bwd_dh(dtd, tw2t, thp, td_lo)
+                ev_td = torch.cuda.Event()
+                ev_td.record(s_td)
+        else:
+            # no live top-down group: the op only zero-fills its six
+            # results; neither s_td nor the top-down half of s_w is used
+            (_, td_dl, td_w1, td_db1, td_w2, td_b2) = ext.grouped_ff_bwd(
+                dtd, None, levels, pos, tw1, tw2, thp, tha, 1, tw1t, tw2t,
+                tdin, td_lo)
         with torch.cuda.stream(s_at):
             s_at.wait_event(ev0)
             dAttn = ext.consensus_bwd(dmix, levels, probs, rnorm,
-                                      ctx.attend_self, mask)
+                                      ctx.attend_self, mask, lo)
         with torch.cuda.stream(s_w):
             s_w.wait_event(ev_bu)
             bu_w1, bu_w2, bu_b2 = ext.ff_bwd_dw(dmix, bu_dh, tokens,
-                                                levels, None, bha, 0)
-            s_w.wait_event(ev_td)
-            td_w1, td_w2, td_b2 = ext.ff_bwd_dw(dtd, td_dh, None, levels,
-                                                pos, tha, 1, tdin)
-        bu_dt, bu_dl = ext.ff_bwd_dx(bu_dh, bw1t, tokens, B, N, L, 0)
-        with torch.cuda.stream(s_td):
-            _, td_dl = ext.ff_bwd_dx(td_dh, tw1t, None, B, N, L, 1)
+                                                levels, None, bha, 0, None,
+                                                lo)
+            if td_live:
+                s_w.wait_event(ev_td)
+                td_w1, td_w2, td_b2 = ext.ff_bwd_dw(dtd, td_dh, None,
+                                                    levels, pos, tha, 1,
+                                                    tdin, td_lo)
+        bu_dt, bu_dl = ext.ff_bwd_dx(bu_dh, bw1t, tokens, B, N, L, 0, lo)
+        if td_live:
+            with torch.cuda.stream(s_td):
+                _, td_dl = ext.ff_bwd_dx(td_dh, tw1t, None, B, N, L, 1,
+                                         td_lo)
         # cross-stream block pinning
-        for t, st in ((dmix, s_at), (dmix, s_w), (dtd, s_td), (dtd, s_w),
-                      (bu_dh, s_w), (td_dh, s_w)):
+        pins = [(dmix, s_at), (dmix, s_w), (bu_dh, s_w)]
+        if td_live:
+            pins += [(dtd, s_td), (dtd, s_w), (td_dh, s_w)]
+        for t, st in pins:
             t.record_stream(st)
-        cur.wait_stream(s_td)
+        if td_live:
+            cur.wait_stream(s_td)
         cur.wait_stream(s_at)
         cur.wait_stream(s_w)
-        for t in (td_db1, td_dl, dAttn, bu_w1, bu_w2, bu_b2,
-                  td_w1, td_w2, td_b2):
+        back = [dAttn, bu_w1, bu_w2, bu_b2]
+        if td_live:
+            back += [td_db1, td_dl, td_w1, td_w2, td_b2]
+        for t in back:
             t.record_stream(cur)
         dLevels = torch.empty_like(levels)
         ext.add4_into(dmix, bu_dl, td_dl, dAttn, dLevels)
         dPos = ext.dpos(td_dl)
         return (bu_dt, dLevels, dPos, bu_w1, bu_db1, bu_w2, bu_b2,
                 td_w1, td_db1, td_w2, td_b2, None, None, None, None, None,
-                None, None, None)
+                None, None, None, None)
 
 
 def _transposed_weights(model):
@@ -381,6 +423,42 @@ def _transposed_weights(model):
 FORCE_SAVE_FOR_BWD = os.environ.get("GLOM_SAVE_HPRE", "0") == "1"
 
 
+# Level-cone check mode (set_check_level_cone / GLOM_CHECK_LEVEL_CONE=1):
+# before each step's backward, test with one host sync that the incoming
+# gradient really is zero below the promised level. Off by default.
+CHECK_LEVEL_CONE = os.environ.get("GLOM_CHECK_LEVEL_CONE", "0") == "1"
+
+
+def set_check_level_cone(on: bool) -> None:
+    global CHECK_LEVEL_CONE
+    CHECK_LEVEL_CONE = bool(on)
+
+
+def level_cone_lo(loss_level_min: int, grad_iters: int, t: int) -> int:
+    """Lowest level in which the gradient arriving at iteration t (that is,
+    at trajectory time t + 1) can be non-zero, when the loss reads time
+    grad_iters at levels >= loss_level_min only: every iteration further
+    back widens the range by one level (bottom-up group g feeds level g
+    from level g - 1; top-down, consensus and the residual never reach
+    further down)."""
+    return max(0, loss_level_min - (grad_iters - 1 - t))
+
+
+def _check_cone(dnew, lo, t):
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError(
+            "the level-cone check synchronises with the host and cannot "
+            "run under stream capture; turn it off (set_check_level_cone"
+            "(False), GLOM_CHECK_LEVEL_CONE=0) or run the step uncaptured")
+    bad = dnew[:, :, :lo].ne(0).any(dim=3).any(dim=1).any(dim=0).tolist()
+    if any(bad):
+        lvl = bad.index(True)
+        raise RuntimeError(
+            f"loss_level_min promise broken: the gradient arriving at "
+            f"iteration {t} is non-zero in level {lvl}, below the first "
+            f"level ({lo}) that loss_level_min allows there")
+
+
 def _needs_bwd(*tensors):
     """Will autograd record a backward through a step on these inputs?
     Must be asked OUTSIDE Function.forward (grad mode is off in there)."""
@@ -390,7 +468,8 @@ def _needs_bwd(*tensors):
         t is not None and t.requires_grad for t in tensors)
 
 
-def glom_step(model, tokens, levels, pos, mask, wts=None, slab_ref=None):
+def glom_step(model, tokens, levels, pos, mask, wts=None, slab_ref=None,
+              cone=None):
     bw = model.bottom_up.net
     tw = model.top_down.net
     if wts is None:
@@ -402,7 +481,7 @@ def glom_step(model, tokens, levels, pos, mask, wts=None, slab_ref=None):
             tw[3].bias)
     return GlomStepFn.apply(
         *args, model.attention.attend_self, mask, *wts, slab_ref,
-        _needs_bwd(*args))
+        _needs_bwd(*args), cone)
 
 
 _TAIL_STREAM = None
@@ -425,15 +504,29 @@ def join_tail_stream():
 
 
 def glom_forward(model, img, iters, levels=None, return_all=False,
-                 grad_iters=None, overlap_tail=False):
+                 grad_iters=None, overlap_tail=False, loss_level_min=None):
     """grad_iters (optional): iterations >= grad_iters run under no_grad.
     Forward VALUES are identical; gradients stop flowing through those
     steps. When a loss only touches trajectory times <= grad_iters (the
     reference's denoising recipe decodes at t=7 of 12), the skipped
     backward contributions are exactly zero — autograd would otherwise
     backprop zeros through every post-loss iteration (reference
-    glom_pytorch.py:131-148 has the same dead work)."""
+    glom_pytorch.py:131-148 has the same dead work).
+
+    loss_level_min (optional, needs grad_iters): the caller promises that
+    the loss reads the trajectory ONLY at time grad_iters and ONLY at
+    levels >= loss_level_min. One iteration moves information by one level
+    at most, so the gradient arriving at iteration t is exactly zero in
+    levels below lo_t = max(0, loss_level_min - (grad_iters - 1 - t)); the
+    backward skips those groups and levels and fills in their zeros. Same
+    values and gradients; a broken promise silently drops gradient unless
+    the check mode (set_check_level_cone) is on."""
     from glom_pytorch_amd.utils.profiling import trace_range
+    if loss_level_min is not None:
+        if grad_iters is None:
+            raise ValueError("loss_level_min requires grad_iters")
+        if not 0 <= loss_level_min < model.levels:
+            raise ValueError("loss_level_min must be a level index")
     b = img.shape[0]
     with trace_range("glom/patch_embed"):
         # K1: hand-written patchify + NT MFMA GEMM, once per forward
@@ -481,8 +574,12 @@ def glom_forward(model, img, iters, levels=None, return_all=False,
                         levels = glom_step(model, tokens, levels, pos,
                                            mask, wts, sref)
                 else:
+                    cone = None
+                    if loss_level_min is not None:
+                        cone = (level_cone_lo(loss_level_min, grad_iters,
+                                              t), t)
                     levels = glom_step(model, tokens, levels, pos, mask,
-                                       wts, sref)
+                                       wts, sref, cone)
             if return_all:
                 steps.append(levels)
         if overlap:

@@ -54,7 +54,7 @@ class DenoisingTrainer:
                  process_group=None, graph_step=True, overlap_tail=True,
                  micro_batches=1, log_path=None, contrast_weight=0.0,
                  contrast_level=-1, contrast_temperature=0.1,
-                 contrast_negatives="other_images"):
+                 contrast_negatives="other_images", level_cone=True):
         """``process_group``: the group whose ranks are data-parallel
         replicas (default: the global group). For 2-D DP x SP meshes pass
         the DP subgroup here — BucketedDDP AVERAGES over its group, which
@@ -77,7 +77,13 @@ class DenoisingTrainer:
         constructor constants, so captured graphs stay keyed on batch shape
         and iters. Micro-batching with the term on is not implemented
         (negatives would have to cross chunks): ``step`` raises
-        ``NotImplementedError``."""
+        ``NotImplementedError``.
+
+        ``level_cone``: pass the model the lowest level the loss reads
+        (``loss_level_min``: the top level, or ``contrast_level`` when the
+        contrastive term is on and lower), so the backward skips the level
+        groups whose gradient is exactly zero. Same losses and updates.
+        Disable with level_cone=False or GLOM_NO_LEVEL_CONE=1."""
         from glom_pytorch_amd.contrast import NEGATIVES
         if contrast_weight < 0 or not contrast_temperature > 0:
             raise ValueError("contrast_weight must be >= 0 and "
@@ -133,6 +139,9 @@ class DenoisingTrainer:
         self.graph_step = (graph_step
                            and os.environ.get("GLOM_NO_GRAPH_STEP", "0")
                            != "1")
+        self.level_cone = (level_cone
+                           and os.environ.get("GLOM_NO_LEVEL_CONE", "0")
+                           != "1")
         self.overlap_tail = (overlap_tail
                              and os.environ.get("GLOM_NO_OVERLAP_TAIL",
                                                 "0") != "1")
@@ -145,6 +154,14 @@ class DenoisingTrainer:
                                                 str(micro_batches)))
         self._micro_stream = None
         self._graphs: dict = {}
+
+    def _loss_level_min(self, contrast: bool = False):
+        """Lowest level the step's loss reads at the decode step, or None
+        with the level cone off."""
+        if not self.level_cone:
+            return None
+        L = self.model.levels
+        return min(L - 1, self.contrast_level % L) if contrast else L - 1
 
     @staticmethod
     def _ops_available():
@@ -197,7 +214,8 @@ class DenoisingTrainer:
         overlap = (self.overlap_tail and img.is_cuda
                    and not getattr(self.model, "force_eager", False))
         all_levels = self.model(noised, iters=iters, return_all=True,
-                                grad_iters=t, overlap_tail=overlap)
+                                grad_iters=t, overlap_tail=overlap,
+                                loss_level_min=self._loss_level_min())
         top = all_levels[t, :, :, -1]
         recon = self.decoder(top)
         loss = F.mse_loss(recon.float(), img.float())
@@ -248,7 +266,8 @@ class DenoisingTrainer:
         overlap = (self.overlap_tail and img.is_cuda
                    and not getattr(self.model, "force_eager", False))
         all_levels = self.model(noised, iters=iters, return_all=True,
-                                grad_iters=t, overlap_tail=overlap)
+                                grad_iters=t, overlap_tail=overlap,
+                                loss_level_min=self._loss_level_min(True))
         recon = self.decoder(all_levels[t, :, :, -1])
         clean = torch.cat((img, img))
         loss = F.mse_loss(recon.float(), clean.float())
@@ -287,7 +306,8 @@ class DenoisingTrainer:
                        scale: float) -> torch.Tensor:
         noised = half + torch.randn_like(half) * self.noise_std
         traj = self.model(noised, iters=iters, return_all=True,
-                          grad_iters=t, overlap_tail=True)
+                          grad_iters=t, overlap_tail=True,
+                          loss_level_min=self._loss_level_min())
         recon = self.decoder(traj[t, :, :, -1])
         return F.mse_loss(recon.float(), half.float()) * scale
 
