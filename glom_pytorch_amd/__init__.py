@@ -19,6 +19,9 @@ from glom_pytorch_amd import islands
 from glom_pytorch_amd.islands import (edge_agreement, labels_from_agreement,
                                       island_labels, island_sizes,
                                       island_count)
+from glom_pytorch_amd import parse
+from glom_pytorch_amd.parse import (ParseTree, island_parents, island_means,
+                                    parse_tree)
 from glom_pytorch_amd import contrast
 from glom_pytorch_amd.contrast import column_contrastive_loss
 
@@ -26,5 +29,6 @@ __version__ = "0.2.0"
 
 __all__ = ["Glom", "GroupedFeedForward", "ConsensusAttention", "islands",
            "edge_agreement", "labels_from_agreement", "island_labels",
-           "island_sizes", "island_count", "contrast",
+           "island_sizes", "island_count", "parse", "ParseTree",
+           "island_parents", "island_means", "parse_tree", "contrast",
            "column_contrastive_loss"]

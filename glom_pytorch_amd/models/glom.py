@@ -258,6 +258,17 @@ class Glom(nn.Module):
         return island_labels(levels, threshold=threshold, grid=(side, side),
                              connectivity=connectivity)
 
+    def parse_tree(self, levels: torch.Tensor, threshold: float = 0.9,
+                   connectivity: int = 4):
+        """Part-whole parse tree of level states ``(*lead, N, L, D)`` on
+        this model's patch grid: a ``ParseTree`` of island labels, sizes,
+        parent links, overlaps and mean vectors (see
+        ``glom_pytorch_amd.parse``); non-differentiable."""
+        from glom_pytorch_amd.parse import parse_tree
+        side = self.num_patches_side
+        return parse_tree(levels, threshold=threshold, grid=(side, side),
+                          connectivity=connectivity)
+
     def contrastive_loss(self, levels_a: torch.Tensor,
                          levels_b: torch.Tensor, level: int = -1,
                          **kw) -> torch.Tensor:

@@ -16,6 +16,7 @@
 #include "aux_kernels.h"
 #include "native_ops.h"
 #include "island_kernels.h"
+#include "parse_kernels.h"
 #include "contrast_kernels.h"
 
 namespace {
@@ -1564,6 +1565,76 @@ std::vector<torch::Tensor> island_sizes(torch::Tensor labels,
 }
 
 // ------------------------------------------------------------------ //
+// parse trees from island labels (glom_pytorch_amd/parse.py): parent links
+// between the islands of adjacent levels and island mean vectors. Like the
+// island ops: no autograd, no host synchronisation.
+
+// labels (*lead, L, H, W) i32 -> {parents, overlap} (*lead, L, H, W) i32
+std::vector<torch::Tensor> island_parents(torch::Tensor labels) {
+    TORCH_CHECK(labels.is_cuda() && labels.is_contiguous()
+                && labels.scalar_type() == at::kInt,
+                "labels must be a contiguous i32 GPU tensor");
+    TORCH_CHECK(labels.dim() >= 3, "labels must be (*lead, L, H, W)");
+    const int64_t nd = labels.dim();
+    const int64_t L = labels.size(nd - 3);
+    const int64_t N = labels.size(nd - 2) * labels.size(nd - 1);
+    TORCH_CHECK(N <= PARSE_MAX_CELLS, "native island parents need N <= ",
+                PARSE_MAX_CELLS);
+    TORCH_CHECK(N > 0 && L > 0, "empty grid");
+    const int64_t PL = labels.numel() / N;
+    TORCH_CHECK(PL <= INT32_MAX && L <= INT32_MAX,
+                "too many (lead, level) problems");
+    auto parents = torch::empty_like(labels);
+    auto overlap = torch::empty_like(labels);
+    launch_island_parents(labels.data_ptr<int>(), parents.data_ptr<int>(),
+                          overlap.data_ptr<int>(), PL, (int)L, (int)N,
+                          cur_stream());
+    check_launch();
+    return {parents, overlap};
+}
+
+// levels (*lead, N, L, D) bf16, labels (*lead, L, H, W) i32 with H*W == N
+// -> means (*lead, N, L, D) f32 or bf16
+torch::Tensor island_means(torch::Tensor levels, torch::Tensor labels,
+                           bool broadcast, bool out_bf16) {
+    CHECK_IN(levels);
+    TORCH_CHECK(labels.is_cuda() && labels.is_contiguous()
+                && labels.scalar_type() == at::kInt,
+                "labels must be a contiguous i32 GPU tensor");
+    TORCH_CHECK(labels.device() == levels.device(),
+                "levels and labels must be on the same device");
+    TORCH_CHECK(levels.dim() >= 3, "levels must be (*lead, N, L, D)");
+    TORCH_CHECK(labels.dim() == levels.dim(),
+                "labels must be (*lead, L, H, W) with the lead of levels");
+    const int64_t nd = levels.dim();
+    const int64_t N = levels.size(nd - 3), L = levels.size(nd - 2),
+                  D = levels.size(nd - 1);
+    for (int64_t i = 0; i < nd - 3; i++)
+        TORCH_CHECK(labels.size(i) == levels.size(i),
+                    "levels and labels must have equal lead dimensions");
+    TORCH_CHECK(labels.size(nd - 3) == L
+                && labels.size(nd - 2) * labels.size(nd - 1) == N,
+                "labels do not match the N and L of levels");
+    TORCH_CHECK(N > 0 && L > 0 && D > 0, "empty levels");
+    TORCH_CHECK(N <= PARSE_MAX_CELLS, "native island means need N <= ",
+                PARSE_MAX_CELLS);
+    TORCH_CHECK(D % 8 == 0, "dim must be a multiple of 8");
+    TORCH_CHECK((uintptr_t)levels.data_ptr() % 16 == 0,
+                "levels must be 16-byte aligned");
+    const int64_t P = levels.numel() / (N * L * D);
+    TORCH_CHECK(P * L <= INT32_MAX && L * D <= INT32_MAX,
+                "too many (lead, level) problems");
+    auto out = torch::empty(
+        levels.sizes(),
+        levels.options().dtype(out_bf16 ? at::kBFloat16 : at::kFloat));
+    launch_island_means(levels.data_ptr(), labels.data_ptr<int>(),
+                        out.data_ptr(), P, (int)N, (int)L, (int)D, broadcast,
+                        out_bf16, cur_stream());
+    check_launch();
+    return out;
+}
+
+// ------------------------------------------------------------------ //
 // column-contrastive loss (glom_pytorch_amd/contrast.py). a, b: (M, D)
 // bf16 with unit column stride and a row stride that is a multiple of 8
 // elements (level slices of a trajectory qualify), M = B * group rows.
@@ -1816,6 +1887,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "island size at each root cell and/or island count",
           py::arg("labels"), py::arg("want_sizes") = true,
           py::arg("want_count") = true);
+    m.def("island_parents", &island_parents,
+          "parent label and overlap of every island one level up");
+    m.def("island_means", &island_means,
+          "mean level-state vector of every island",
+          py::arg("levels"), py::arg("labels"), py::arg("broadcast"),
+          py::arg("out_bf16"));
     m.def("nce_fwd", &nce_fwd,
           "column-contrastive loss forward: (M,D) bf16 a, b -> "
           "{loss, lse, ra, rb}");

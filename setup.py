@@ -23,6 +23,7 @@ ext = CUDAExtension(
         "glom_pytorch_amd/ops/csrc/aux_kernels.hip",
         "glom_pytorch_amd/ops/csrc/native_ops.hip",
         "glom_pytorch_amd/ops/csrc/island_kernels.hip",
+        "glom_pytorch_amd/ops/csrc/parse_kernels.hip",
         "glom_pytorch_amd/ops/csrc/contrast_kernels.hip",
     ],
     extra_compile_args={
