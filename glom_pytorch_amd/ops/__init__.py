@@ -58,6 +58,25 @@ def native_forward(model, img, iters, levels=None, return_all=False,
                         loss_level_min=loss_level_min)
 
 
+def set_token_hoist(on: bool) -> None:
+    """Token-MLP hoist (default on; ``GLOM_NO_TOKEN_HOIST=1`` turns it off):
+    bottom-up group 0 reads only the tokens, so it runs in iteration 0 of a
+    forward and afterwards only at steps whose backward reads its
+    pre-activations. Values and gradients are bit-identical either way.
+    Read once per forward."""
+    from glom_pytorch_amd.ops import functional
+    functional.set_token_hoist(on)
+
+
+def set_mix_fusion(on: bool) -> None:
+    """Level-mix fusion (default on; ``GLOM_NO_MIX_FUSION=1`` turns it off):
+    the level mix also writes the next iteration's top-down input and row
+    norms (dim 512; other dims keep the standalone kernels). Bit-identical
+    either way. Read once per forward."""
+    from glom_pytorch_amd.ops import functional
+    functional.set_mix_fusion(on)
+
+
 def set_check_level_cone(on: bool) -> None:
     """Level-cone check mode: before each step's backward, verify with one
     host sync that the gradient is zero below the level ``loss_level_min``

@@ -18,9 +18,16 @@ void launch_knorm_combine(const void* dkhat, const void* lev,
                           const float* rnorm, const void* dv, const void* dq,
                           void* out, int B, int N, int L, int d,
                           hipStream_t s, int l_lo = 0);
+// bu0 (optional, row stride bu0_ld elements): level 0 of `bu` is read from
+// there. td_next / rn_next (optional, both or neither; need pos, N and
+// mix_fwd_can_emit_next): k_add_pos / k_rnorm of `out`, written by the mix
 void launch_mix_fwd(const void* prev, const void* bu, const void* td,
                     const void* cons, void* out, long total, int L, int d,
-                    hipStream_t s);
+                    hipStream_t s, const void* bu0 = nullptr,
+                    long bu0_ld = 0, const void* pos = nullptr,
+                    void* td_next = nullptr, float* rn_next = nullptr,
+                    int N = 1);
+bool mix_fwd_can_emit_next(int L, int d);
 void launch_mix_bwd(const void* dout, void* dmix, void* dtd, long total,
                     int L, int d, hipStream_t s);
 void launch_add4(const void* a, const void* b, const void* c, const void* d,

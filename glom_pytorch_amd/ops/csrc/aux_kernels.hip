@@ -273,10 +273,25 @@ __global__ __launch_bounds__(NTHREADS) void k_knorm_combine(
 
 // out = (prev + bu + td_padded + cons) / c_l, elementwise over (B,N,L,d);
 // td has L-1 level slots, the top slot contributes zero.
+// bu0 (optional): level 0 of the bottom-up contribution comes from
+// bu0 + bn * bu0_ld instead of bu's slice 0, which is then never read (the
+// token MLP is loop-invariant, docs/ARCHITECTURE.md "Loop invariants").
+// NEXT: also write, from the bf16-rounded values being stored, what the
+// next iteration's k_add_pos and k_rnorm would compute from `out`:
+//   td_next[b,n,l-1,:] = out[b,n,l,:] + pos[n,:]        (l >= 1)
+//   rn_next[b,l,n]     = 1 / max(||out[b,n,l,:]||, 1e-12)
+// Only for d == WAVE * 8 (512): one wave then holds exactly one row with
+// lane -> q0 = lane * 8, which is k_rnorm's map, so the eight sequential
+// adds and the wave_reduce_sum below repeat its summation order bit for
+// bit. Other d keep the standalone kernels (the host never asks for NEXT).
+template <bool NEXT>
 __global__ __launch_bounds__(NTHREADS) void k_mix_fwd(
         const ushort_t* __restrict__ prev, const ushort_t* __restrict__ bu,
         const ushort_t* __restrict__ td, const ushort_t* __restrict__ cons,
-        ushort_t* __restrict__ out, long total, int L, int d) {
+        ushort_t* __restrict__ out, long total, int L, int d,
+        const ushort_t* __restrict__ bu0, long bu0_ld,
+        const ushort_t* __restrict__ pos, ushort_t* __restrict__ td_next,
+        float* __restrict__ rn_next, int N) {
     long idx = ((long)blockIdx.x * NTHREADS + threadIdx.x) * 8;
     if (idx >= total) return;
     int q = idx % d;
@@ -284,7 +299,8 @@ __global__ __launch_bounds__(NTHREADS) void k_mix_fwd(
     long bn = idx / ((long)d * L);
     union { uint4v v; ushort_t u[8]; } a, b, c4, t, o;
     a.v = *(const uint4v*)(prev + idx);
-    b.v = *(const uint4v*)(bu + idx);
+    b.v = *(const uint4v*)((bu0 && l == 0) ? bu0 + bn * bu0_ld + q
+                                           : bu + idx);
     c4.v = *(const uint4v*)(cons + idx);
     bool has_td = l < L - 1;
     if (has_td) t.v = *(const uint4v*)(td + (bn * (L - 1) + l) * (long)d + q);
@@ -296,6 +312,29 @@ __global__ __launch_bounds__(NTHREADS) void k_mix_fwd(
         o.u[e] = f2bf(v / c);
     }
     *(uint4v*)(out + idx) = o.v;
+    if (NEXT) {
+        // d == WAVE * 8: the wave is whole (total is a multiple of d) and
+        // l, bn are wave-uniform
+        long n = bn % N;
+        long bb = bn / N;
+        float ss = 0.f;
+#pragma unroll
+        for (int e = 0; e < 8; e++) {
+            float v = bf2f(o.u[e]);
+            ss += v * v;
+        }
+        ss = wave_reduce_sum(ss);
+        if (threadIdx.x % WAVE == 0)
+            rn_next[(bb * L + l) * N + n] = 1.0f / fmaxf(sqrtf(ss), 1e-12f);
+        if (l >= 1) {
+            union { uint4v v; ushort_t u[8]; } p;
+            p.v = *(const uint4v*)(pos + n * (long)d + q);
+#pragma unroll
+            for (int e = 0; e < 8; e++)
+                p.u[e] = f2bf(bf2f(o.u[e]) + bf2f(p.u[e]));
+            *(uint4v*)(td_next + (bn * (L - 1) + l - 1) * (long)d + q) = p.v;
+        }
+    }
 }
 
 // dmix = dout / c_l (shared by prev/bu/cons); dtd = dout[..., :L-1, :] / 4
@@ -391,12 +430,26 @@ void launch_knorm_combine(const void* dkhat, const void* lev,
 
 void launch_mix_fwd(const void* prev, const void* bu, const void* td,
                     const void* cons, void* out, long total, int L, int d,
-                    hipStream_t s) {
-    hipLaunchKernelGGL(k_mix_fwd, dim3(cdiv(total / 8, NTHREADS)), dim3(NTHREADS),
-                       0, s, (const ushort_t*)prev, (const ushort_t*)bu,
-                       (const ushort_t*)td, (const ushort_t*)cons,
-                       (ushort_t*)out, total, L, d);
+                    hipStream_t s, const void* bu0, long bu0_ld,
+                    const void* pos, void* td_next, float* rn_next, int N) {
+    dim3 grid(cdiv(total / 8, NTHREADS)), block(NTHREADS);
+    if (td_next)
+        hipLaunchKernelGGL(k_mix_fwd<true>, grid, block, 0, s,
+                           (const ushort_t*)prev, (const ushort_t*)bu,
+                           (const ushort_t*)td, (const ushort_t*)cons,
+                           (ushort_t*)out, total, L, d, (const ushort_t*)bu0,
+                           bu0_ld, (const ushort_t*)pos, (ushort_t*)td_next,
+                           rn_next, N);
+    else
+        hipLaunchKernelGGL(k_mix_fwd<false>, grid, block, 0, s,
+                           (const ushort_t*)prev, (const ushort_t*)bu,
+                           (const ushort_t*)td, (const ushort_t*)cons,
+                           (ushort_t*)out, total, L, d, (const ushort_t*)bu0,
+                           bu0_ld, (const ushort_t*)nullptr,
+                           (ushort_t*)nullptr, (float*)nullptr, N);
 }
+
+bool mix_fwd_can_emit_next(int L, int d) { return d == WAVE * 8 && L >= 2; }
 
 void launch_mix_bwd(const void* dout, void* dmix, void* dtd, long total,
                     int L, int d, hipStream_t s) {

@@ -452,12 +452,23 @@ std::vector<torch::Tensor> grouped_ff_fwd(
         c10::optional<torch::Tensor> tokens_opt, torch::Tensor levels,
         c10::optional<torch::Tensor> pos_opt, torch::Tensor w1,
         torch::Tensor b1, torch::Tensor w2, torch::Tensor b2, int64_t mode,
-        bool save_for_bwd = true) {
+        bool save_for_bwd = true, bool group0_done = false,
+        c10::optional<torch::Tensor> td_in_ready = c10::nullopt) {
     CHECK_IN(levels); CHECK_IN(w1); CHECK_IN(b1); CHECK_IN(w2); CHECK_IN(b2);
     const int64_t B = levels.size(0), N = levels.size(1),
                   L = levels.size(2), d = levels.size(3);
     const int64_t G = (mode == 0) ? L : L - 1;
     TORCH_CHECK(G <= GEMM_MAX_TABLE, "levels > 16 unsupported by table mode");
+    // group0_done (bottom-up only): group 0 reads `tokens`, not `levels`,
+    // so within one forward its results repeat bit for bit; the caller kept
+    // them from an earlier call and nothing will read this call's. Both
+    // GEMMs then run groups [1, G) (bases and tables offset by one group,
+    // gates judged by the full G, as the level cone does in the backward):
+    // Y[:, :, 0], Hpre[0] and Hact[0] are left unwritten.
+    TORCH_CHECK(!group0_done || (mode == 0 && G >= 2),
+                "group0_done needs the bottom-up mode and levels >= 2");
+    const int64_t g0 = group0_done ? 1 : 0;
+    const int64_t Ga = G - g0;
     const int64_t m4 = w1.size(0) / G;
     const int64_t M = B * N;
     TORCH_CHECK(d % 8 == 0 && m4 % 8 == 0, "dim and mult*dim must be /8");
@@ -487,56 +498,74 @@ std::vector<torch::Tensor> grouped_ff_fwd(
         TORCH_CHECK(pos_opt.has_value(), "top-down needs pos");
         auto pos = pos_opt.value();
         CHECK_IN(pos);
-        td_in = torch::empty({B, N, G, d}, opts);
-        launch_add_pos(levels.data_ptr(), pos.data_ptr(), td_in.data_ptr(),
-                       td_in.numel(), (int)N, (int)L, (int)d, s);
-        check_launch();
+        if (td_in_ready.has_value()) {
+            // the previous iteration's level mix already wrote it
+            td_in = td_in_ready.value();
+            CHECK_IN(td_in);
+            TORCH_CHECK(td_in.dim() == 4 && td_in.size(0) == B
+                        && td_in.size(1) == N && td_in.size(2) == G
+                        && td_in.size(3) == d, "td_in must be (B,N,L-1,d)");
+        } else {
+            td_in = torch::empty({B, N, G, d}, opts);
+            launch_add_pos(levels.data_ptr(), pos.data_ptr(),
+                           td_in.data_ptr(), td_in.numel(), (int)N, (int)L,
+                           (int)d, s);
+            check_launch();
+        }
     }
 
     // up-projection: Hpre_g = x_g @ W1_g^T + b1_g ; Hact_g = gelu(Hpre_g)
     {
-        GemmParams p = base_params(M, m4, d, LAYOUT_NT, G, G, 1.0f);
+        GemmParams p = base_params(M, m4, d, LAYOUT_NT, Ga, Ga, 1.0f);
         if (mode == 0) {
             TORCH_CHECK(tokens_opt.has_value(), "bottom-up needs tokens");
             auto tokens = tokens_opt.value();
             CHECK_IN(tokens);
+            TORCH_CHECK(tokens.numel() == M * d, "tokens must be (B,N,d)");
             p.A.flags = OP_TABLE;
-            p.Atab[0] = tokens.data_ptr();
-            p.Atabld[0] = d;
+            if (g0 == 0) {
+                p.Atab[0] = tokens.data_ptr();
+                p.Atabld[0] = d;
+            }
             for (int64_t g = 1; g < G; g++) {
-                p.Atab[g] = (const char*)levels.data_ptr() + (g - 1) * d * 2;
-                p.Atabld[g] = L * d;
+                p.Atab[g - g0] = (const char*)levels.data_ptr()
+                                 + (g - 1) * d * 2;
+                p.Atabld[g - g0] = L * d;
             }
         } else {
             p.A.base = td_in.data_ptr();
             p.A.sin = d; p.A.ld = G * d;
         }
-        p.B.base = w1.data_ptr(); p.B.sin = m4 * d; p.B.ld = d;
-        p.Cbase = Hpre.data_ptr(); p.Csin = M * m4; p.Cld = m4;
-        p.bias_base = b1.data_ptr(); p.bias_sin = m4; p.has_bias = 1;
+        p.B.base = u16_at(w1, g0 * m4 * d); p.B.sin = m4 * d; p.B.ld = d;
+        p.Csin = M * m4; p.Cld = m4;
+        p.bias_base = u16_at(b1, g0 * m4); p.bias_sin = m4; p.has_bias = 1;
         if (gelu_only) {
             p.epilogue = EPI_GELU;
-            p.Cbase = Hact.data_ptr();
-        } else if (pair) {
-            p.epilogue = EPI_GELU_PAIR;
-            p.out2 = Hact.data_ptr();
-            p.out2_sin = M * m4; p.out2_ld = m4;
+            p.Cbase = u16_at(Hact, g0 * M * m4);
+        } else {
+            p.Cbase = u16_at(Hpre, g0 * M * m4);
+            if (pair) {
+                p.epilogue = EPI_GELU_PAIR;
+                p.out2 = u16_at(Hact, g0 * M * m4);
+                p.out2_sin = M * m4; p.out2_ld = m4;
+            }
         }
-        run_gemm(p, s, opts, true);
+        run_gemm(p, s, opts, true, G);
         if (!pair) {
             // activation as its own bandwidth-bound pass (round-1 default)
-            launch_gelu(Hpre.data_ptr(), Hact.data_ptr(), Hpre.numel(), s);
+            launch_gelu(u16_at(Hpre, g0 * M * m4), u16_at(Hact, g0 * M * m4),
+                        Ga * M * m4, s);
             check_launch();
         }
     }
     // down-projection: Y_g = Hact_g @ W2_g^T + b2_g
     {
-        GemmParams p = base_params(M, d, m4, LAYOUT_NT, G, G, 1.0f);
-        p.A.base = Hact.data_ptr(); p.A.sin = M * m4; p.A.ld = m4;
-        p.B.base = w2.data_ptr(); p.B.sin = d * m4; p.B.ld = m4;
-        p.Cbase = (char*)Y.data_ptr() ; p.Csin = d; p.Cld = G * d;
-        p.bias_base = b2.data_ptr(); p.bias_sin = d; p.has_bias = 1;
-        run_gemm(p, s, opts, true);
+        GemmParams p = base_params(M, d, m4, LAYOUT_NT, Ga, Ga, 1.0f);
+        p.A.base = u16_at(Hact, g0 * M * m4); p.A.sin = M * m4; p.A.ld = m4;
+        p.B.base = u16_at(w2, g0 * d * m4); p.B.sin = d * m4; p.B.ld = m4;
+        p.Cbase = u16_at(Y, g0 * d); p.Csin = d; p.Cld = G * d;
+        p.bias_base = u16_at(b2, g0 * d); p.bias_sin = d; p.has_bias = 1;
+        run_gemm(p, s, opts, true, G);
     }
     if (mode != 1) td_in = torch::empty({0}, opts);
     if (!save_for_bwd) Hpre = torch::empty({0}, opts);
@@ -718,7 +747,8 @@ std::vector<torch::Tensor> grouped_ff_bwd(
 
 std::vector<torch::Tensor> consensus_fwd(
         torch::Tensor levels, bool attend_self,
-        c10::optional<torch::Tensor> mask_opt) {
+        c10::optional<torch::Tensor> mask_opt,
+        c10::optional<torch::Tensor> rnorm_ready = c10::nullopt) {
     CHECK_IN(levels);
     const int64_t B = levels.size(0), N = levels.size(1),
                   L = levels.size(2), d = levels.size(3);
@@ -734,10 +764,21 @@ std::vector<torch::Tensor> consensus_fwd(
     }
 
     const bool lds_ok = (N % 8 == 0) && (d % 8 == 0);
-    auto rnorm = torch::empty({B, L, N}, opts.dtype(at::kFloat));
-    launch_rnorm(levels.data_ptr(), rnorm.data_ptr<float>(),
-                 (int)B, (int)N, (int)L, (int)d, s);
-    check_launch();
+    torch::Tensor rnorm;
+    if (rnorm_ready.has_value()) {
+        // the previous iteration's level mix already wrote it
+        rnorm = rnorm_ready.value();
+        TORCH_CHECK(rnorm.is_cuda() && rnorm.is_contiguous()
+                    && rnorm.scalar_type() == at::kFloat
+                    && rnorm.dim() == 3 && rnorm.size(0) == B
+                    && rnorm.size(1) == L && rnorm.size(2) == N,
+                    "rnorm must be f32 (B,L,N)");
+    } else {
+        rnorm = torch::empty({B, L, N}, opts.dtype(at::kFloat));
+        launch_rnorm(levels.data_ptr(), rnorm.data_ptr<float>(),
+                     (int)B, (int)N, (int)L, (int)d, s);
+        check_launch();
+    }
 
     auto probs = torch::empty({B, L, N, N}, opts);
     const bool fused_sm = (N == 256) && (d % 64 == 0) && lds_ok;
@@ -923,13 +964,51 @@ torch::Tensor consensus_bwd(torch::Tensor dOut, torch::Tensor levels,
 // slab[slab_idx] and returned as an untracked alias — the return_all
 // trajectory is then materialized in place, with no torch.stack copy
 // (SURVEY.md §2.3 note on the trajectory slab).
-torch::Tensor level_mix_fwd(torch::Tensor levels, torch::Tensor bu,
-                            torch::Tensor td, torch::Tensor cons,
-                            c10::optional<torch::Tensor> slab = c10::nullopt,
-                            int64_t slab_idx = 0) {
+//
+// bu0 (optional): a (B,N,d) view, rows contiguous and evenly strided, that
+// holds level 0 of the bottom-up contribution; slice 0 of `bu` is then not
+// read. glom_forward passes iteration 0's Y[:, :, 0, :] (row stride L*d), so
+// no compact copy is made and nothing is copied back into later Ys.
+//
+// pos (optional): also produce the next iteration's top-down input and row
+// norms from the rounded output (see k_mix_fwd). Returns {out, td_next,
+// rn_next}; the last two are empty where the mix kernel does not emit them
+// (d != 512), and the consumers then run k_add_pos / k_rnorm as before.
+std::vector<torch::Tensor> level_mix_fwd_next(
+        torch::Tensor levels, torch::Tensor bu, torch::Tensor td,
+        torch::Tensor cons, c10::optional<torch::Tensor> slab = c10::nullopt,
+        int64_t slab_idx = 0, c10::optional<torch::Tensor> bu0 = c10::nullopt,
+        c10::optional<torch::Tensor> pos = c10::nullopt) {
     CHECK_IN(levels); CHECK_IN(bu); CHECK_IN(td); CHECK_IN(cons);
-    const int64_t L = levels.size(2), d = levels.size(3);
+    const int64_t B = levels.size(0), N = levels.size(1),
+                  L = levels.size(2), d = levels.size(3);
     TORCH_CHECK(d % 8 == 0, "dim must be a multiple of 8");
+    TORCH_CHECK(bu.numel() == levels.numel() && cons.numel() == levels.numel()
+                && td.numel() == B * N * (L - 1) * d,
+                "level mix operands do not match levels");
+    const void* bu0_ptr = nullptr;
+    int64_t bu0_ld = 0;
+    if (bu0.has_value()) {
+        const auto& t = bu0.value();
+        TORCH_CHECK(t.is_cuda() && t.scalar_type() == at::kBFloat16
+                    && t.dim() == 3 && t.size(0) == B && t.size(1) == N
+                    && t.size(2) == d && t.stride(2) == 1
+                    && t.stride(1) >= d && t.stride(1) % 8 == 0
+                    && t.stride(0) == N * t.stride(1)
+                    && ((uintptr_t)t.data_ptr() & 15) == 0,
+                    "bu0 must be an evenly strided (B,N,d) bf16 view");
+        bu0_ptr = t.data_ptr();
+        bu0_ld = t.stride(1);
+    }
+    const bool emit = pos.has_value() && mix_fwd_can_emit_next((int)L, (int)d);
+    auto td_next = torch::empty({0}, levels.options());
+    auto rn_next = torch::empty({0}, levels.options().dtype(at::kFloat));
+    if (emit) {
+        CHECK_IN(pos.value());
+        TORCH_CHECK(pos->numel() == N * d, "pos must be (N,d)");
+        td_next = torch::empty({B, N, L - 1, d}, levels.options());
+        rn_next = torch::empty({B, L, N}, levels.options().dtype(at::kFloat));
+    }
     torch::Tensor out;
     if (slab.has_value()) {
         TORCH_CHECK(slab->is_contiguous()
@@ -942,9 +1021,21 @@ torch::Tensor level_mix_fwd(torch::Tensor levels, torch::Tensor bu,
     }
     launch_mix_fwd(levels.data_ptr(), bu.data_ptr(), td.data_ptr(),
                    cons.data_ptr(), out.data_ptr(), levels.numel(), (int)L,
-                   (int)d, cur_stream());
+                   (int)d, cur_stream(), bu0_ptr, bu0_ld,
+                   emit ? pos->data_ptr() : nullptr,
+                   emit ? td_next.data_ptr() : nullptr,
+                   emit ? rn_next.data_ptr<float>() : nullptr, (int)N);
     check_launch();
-    return out;
+    return {out, td_next, rn_next};
+}
+
+torch::Tensor level_mix_fwd(torch::Tensor levels, torch::Tensor bu,
+                            torch::Tensor td, torch::Tensor cons,
+                            c10::optional<torch::Tensor> slab = c10::nullopt,
+                            int64_t slab_idx = 0,
+                            c10::optional<torch::Tensor> bu0 = c10::nullopt) {
+    return level_mix_fwd_next(levels, bu, td, cons, slab, slab_idx, bu0,
+                              c10::nullopt)[0];
 }
 
 std::vector<torch::Tensor> level_mix_bwd(torch::Tensor dout) {
@@ -976,14 +1067,28 @@ std::vector<torch::Tensor> glom_step_fwd(
         torch::Tensor tw2, torch::Tensor tb2, bool attend_self,
         c10::optional<torch::Tensor> mask,
         c10::optional<torch::Tensor> slab = c10::nullopt,
-        int64_t slab_idx = 0, bool save_for_bwd = true) {
+        int64_t slab_idx = 0, bool save_for_bwd = true,
+        c10::optional<torch::Tensor> bu0 = c10::nullopt,
+        c10::optional<torch::Tensor> td_in_ready = c10::nullopt,
+        c10::optional<torch::Tensor> rnorm_ready = c10::nullopt,
+        bool emit_next = false) {
+    // bu0: level 0 of the bottom-up output, kept from iteration 0 of this
+    // forward; the token MLP (group 0) is then skipped here.
+    // td_in_ready / rnorm_ready: written by the previous iteration's mix.
+    // emit_next: this mix writes them for the next one; results 8 and 9
+    // (empty where the mix does not emit, see level_mix_fwd_next)
     auto bu = grouped_ff_fwd(tokens, levels, c10::nullopt, bw1, bb1, bw2,
-                             bb2, 0, save_for_bwd);
+                             bb2, 0, save_for_bwd, bu0.has_value());
     auto td = grouped_ff_fwd(c10::nullopt, levels, pos, tw1, tb1, tw2,
-                             tb2, 1, save_for_bwd);
-    auto at = consensus_fwd(levels, attend_self, mask);
-    auto out = level_mix_fwd(levels, bu[0], td[0], at[0], slab, slab_idx);
-    return {out, bu[1], bu[2], td[1], td[2], at[1], at[2], td[3]};
+                             tb2, 1, save_for_bwd, false, td_in_ready);
+    auto at = consensus_fwd(levels, attend_self, mask, rnorm_ready);
+    auto mx = level_mix_fwd_next(
+        levels, bu[0], td[0], at[0], slab, slab_idx, bu0,
+        emit_next ? c10::optional<torch::Tensor>(pos) : c10::nullopt);
+    std::vector<torch::Tensor> r = {mx[0], bu[1], bu[2], td[1], td[2],
+                                    at[1], at[2], td[3]};
+    if (emit_next) { r.push_back(mx[1]); r.push_back(mx[2]); }
+    return r;
 }
 
 std::vector<torch::Tensor> glom_step_bwd(
@@ -1806,7 +1911,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("grouped_ff_fwd", &grouped_ff_fwd, "grouped FF forward",
           py::arg("tokens"), py::arg("levels"), py::arg("pos"),
           py::arg("w1"), py::arg("b1"), py::arg("w2"), py::arg("b2"),
-          py::arg("mode"), py::arg("save_for_bwd") = true);
+          py::arg("mode"), py::arg("save_for_bwd") = true,
+          py::arg("group0_done") = false,
+          py::arg("td_in") = c10::nullopt);
     m.def("grouped_ff_bwd", &grouped_ff_bwd, "grouped FF backward",
           py::arg("dY"), py::arg("tokens"), py::arg("levels"),
           py::arg("pos"), py::arg("w1"), py::arg("w2"),
@@ -1814,14 +1921,22 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("w1t") = c10::nullopt,
           py::arg("w2t") = c10::nullopt,
           py::arg("td_in") = c10::nullopt, py::arg("g_lo") = 0);
-    m.def("consensus_fwd", &consensus_fwd, "consensus attention forward");
+    m.def("consensus_fwd", &consensus_fwd, "consensus attention forward",
+          py::arg("levels"), py::arg("attend_self"), py::arg("mask"),
+          py::arg("rnorm") = c10::nullopt);
     m.def("consensus_bwd", &consensus_bwd, "consensus attention backward",
           py::arg("dOut"), py::arg("levels"), py::arg("probs"),
           py::arg("rnorm"), py::arg("attend_self"), py::arg("mask"),
           py::arg("l_lo") = 0);
     m.def("level_mix_fwd", &level_mix_fwd, "level mix forward",
           py::arg("levels"), py::arg("bu"), py::arg("td"), py::arg("cons"),
-          py::arg("slab") = c10::nullopt, py::arg("slab_idx") = 0);
+          py::arg("slab") = c10::nullopt, py::arg("slab_idx") = 0,
+          py::arg("bu0") = c10::nullopt);
+    m.def("level_mix_fwd_next", &level_mix_fwd_next,
+          "level mix forward, also emitting the next td_in / rnorm",
+          py::arg("levels"), py::arg("bu"), py::arg("td"), py::arg("cons"),
+          py::arg("slab") = c10::nullopt, py::arg("slab_idx") = 0,
+          py::arg("bu0") = c10::nullopt, py::arg("pos") = c10::nullopt);
     m.def("level_mix_bwd", &level_mix_bwd, "level mix backward");
     m.def("glom_step_fwd", &glom_step_fwd, "full GLOM iteration forward",
           py::arg("tokens"), py::arg("levels"), py::arg("pos"),
@@ -1829,7 +1944,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("tw1"), py::arg("tb1"), py::arg("tw2"), py::arg("tb2"),
           py::arg("attend_self"), py::arg("mask"),
           py::arg("slab") = c10::nullopt, py::arg("slab_idx") = 0,
-          py::arg("save_for_bwd") = true);
+          py::arg("save_for_bwd") = true, py::arg("bu0") = c10::nullopt,
+          py::arg("td_in") = c10::nullopt, py::arg("rnorm") = c10::nullopt,
+          py::arg("emit_next") = false);
     m.def("glom_step_bwd", &glom_step_bwd, "full GLOM iteration backward",
           py::arg("dnew"), py::arg("tokens"), py::arg("levels"),
           py::arg("pos"), py::arg("bw1"), py::arg("bw2"), py::arg("tw1"),

@@ -212,7 +212,7 @@ class GlomStepFn(torch.autograd.Function):
     def forward(ctx, tokens, levels, pos, bw1, bb1, bw2, bb2,
                 tw1, tb1, tw2, tb2, attend_self, mask,
                 bw1t, bw2t, tw1t, tw2t, slab_ref=None,
-                save_for_bwd=True, cone=None):
+                save_for_bwd=True, cone=None, carry=None):
         # slab_ref: optional (slab, idx) — write the step output straight
         # into the preallocated trajectory slab (untracked alias return)
         # save_for_bwd: False on forward-only steps (decided by glom_step,
@@ -222,7 +222,14 @@ class GlomStepFn(torch.autograd.Function):
         # arriving at this step (iteration t) is zero in levels < lo. The
         # backward then runs the groups / levels >= lo only. With lo = L-1
         # no top-down group is live, so its pre-activations are not kept
+        # carry: None, or glom_forward's _LoopCarry (not differentiable):
+        # the kept token-MLP output, what the previous step's mix prepared
+        # for this one, and what this step's mix is to prepare
         ext = _load_extension()
+        bu0 = carry.bu0 if carry is not None and carry.skip0 else None
+        td_ready = carry.td_in if carry is not None else None
+        rn_ready = carry.rnorm if carry is not None else None
+        emit = carry is not None and carry.emit
         slab, sidx = slab_ref if slab_ref is not None else (None, 0)
         lo = cone[0] if cone is not None else 0
         save_td = save_for_bwd and (lo < levels.size(2) - 1
@@ -236,6 +243,8 @@ class GlomStepFn(torch.autograd.Function):
              tdin) = ext.glom_step_fwd(
                 tokens, levels, pos, bw1, bb1, bw2, bb2, tw1, tb1, tw2,
                 tb2, attend_self, mask, slab, sidx, save_for_bwd)
+            if carry is not None:
+                carry.set_next(None, None)
         else:
             # the three per-iteration chains (bottom-up MLP, top-down MLP,
             # consensus attention) only depend on `levels`; forking them
@@ -247,17 +256,19 @@ class GlomStepFn(torch.autograd.Function):
             ev.record(cur)
             buY, bhp, bha, _ = ext.grouped_ff_fwd(tokens, levels, None,
                                                   bw1, bb1, bw2, bb2, 0,
-                                                  save_for_bwd)
+                                                  save_for_bwd,
+                                                  bu0 is not None)
             with torch.cuda.stream(s_td):
                 s_td.wait_event(ev)
                 tdY, thp, tha, tdin = ext.grouped_ff_fwd(None, levels, pos,
                                                          tw1, tb1, tw2,
                                                          tb2, 1,
-                                                         save_td)
+                                                         save_td, False,
+                                                         td_ready)
             with torch.cuda.stream(s_at):
                 s_at.wait_event(ev)
                 cons, probs, rnorm = ext.consensus_fwd(levels, attend_self,
-                                                       mask)
+                                                       mask, rn_ready)
             cur.wait_stream(s_td)
             cur.wait_stream(s_at)
             # boundary tensors crossing back to the main stream: pin their
@@ -265,7 +276,19 @@ class GlomStepFn(torch.autograd.Function):
             for t in (tdY, thp, tha, tdin, cons, probs, rnorm):
                 if t.numel():
                     t.record_stream(cur)
-            out = ext.level_mix_fwd(levels, buY, tdY, cons, slab, sidx)
+            if emit:
+                out, td_next, rn_next = ext.level_mix_fwd_next(
+                    levels, buY, tdY, cons, slab, sidx, bu0, pos)
+                carry.set_next(td_next, rn_next)
+            else:
+                out = ext.level_mix_fwd(levels, buY, tdY, cons, slab, sidx,
+                                        bu0)
+                if carry is not None:
+                    carry.set_next(None, None)
+            if carry is not None and carry.hoist and carry.bu0 is None:
+                # this step ran every group: keep its token-MLP output (a
+                # view into Y, row stride L*d) for the rest of the forward
+                carry.bu0 = buY[:, :, 0, :]
         ctx.save_for_backward(tokens, levels, pos, bw1, bw2, tw1, tw2,
                               bhp, bha, thp, tha, probs, rnorm, mask,
                               bw1t, bw2t, tw1t, tw2t, tdin)
@@ -296,7 +319,7 @@ class GlomStepFn(torch.autograd.Function):
                 bw1t, bw2t, tw1t, tw2t, tdin, lo)
             return (dTokens, dLevels, dPos, dbw1, dbb1, dbw2, dbb2,
                     dtw1, dtb1, dtw2, dtb2, None, None, None, None, None,
-                    None, None, None, None)
+                    None, None, None, None, None)
         if os.environ.get("GLOM_BWD_FORK", "3") == "3":
             cur = torch.cuda.current_stream()
             s_td, s_at, _ = GlomStepFn._side_streams()
@@ -333,7 +356,7 @@ class GlomStepFn(torch.autograd.Function):
             dPos = ext.dpos(td[1])
             return (bu[0], dLevels, dPos, bu[2], bu[3], bu[4], bu[5],
                     td[2], td[3], td[4], td[5], None, None, None, None,
-                    None, None, None, None, None)
+                    None, None, None, None, None, None)
         # 4-way fork variant (weight grads on a dedicated stream): measured
         # slightly SLOWER than the 3-way fork above (sync overhead), kept
         # behind GLOM_BWD_FORK=4 for future tuning.
@@ -397,7 +420,7 @@ class GlomStepFn(torch.autograd.Function):
         dPos = ext.dpos(td_dl)
         return (bu_dt, dLevels, dPos, bu_w1, bu_db1, bu_w2, bu_b2,
                 td_w1, td_db1, td_w2, td_b2, None, None, None, None, None,
-                None, None, None, None)
+                None, None, None, None, None)
 
 
 def _transposed_weights(model):
@@ -432,6 +455,62 @@ CHECK_LEVEL_CONE = os.environ.get("GLOM_CHECK_LEVEL_CONE", "0") == "1"
 def set_check_level_cone(on: bool) -> None:
     global CHECK_LEVEL_CONE
     CHECK_LEVEL_CONE = bool(on)
+
+
+# Loop invariants (docs/ARCHITECTURE.md "Loop invariants"), each with a
+# switch that is read once per glom_forward call, so both settings can be
+# compared within one process:
+#   token hoist  set_token_hoist / GLOM_NO_TOKEN_HOIST=1 — bottom-up group 0
+#                (the token MLP) runs in iteration 0 and again only at steps
+#                whose backward reads its pre-activations
+#   mix fusion   set_mix_fusion / GLOM_NO_MIX_FUSION=1 — the level mix also
+#                writes the next iteration's td_in and rnorm
+TOKEN_HOIST = True
+MIX_FUSION = True
+
+
+def set_token_hoist(on: bool) -> None:
+    global TOKEN_HOIST
+    TOKEN_HOIST = bool(on)
+
+
+def set_mix_fusion(on: bool) -> None:
+    global MIX_FUSION
+    MIX_FUSION = bool(on)
+
+
+class _LoopCarry:
+    """What one glom_forward call carries from iteration to iteration
+    besides `levels`. None of it is differentiable.
+
+    bu0:    (B,N,d) view of iteration 0's bottom-up output, level 0; set by
+            the first step that runs every group, then read by the level
+            mix of every step that skips group 0
+    skip0:  decided per step by glom_step (outside Function.forward)
+    td_in, rnorm: written by the previous step's mix for this step, or None
+    emit:   this step's mix is to write them for the next step"""
+
+    def __init__(self, levels):
+        two = levels.size(2) >= 2
+        self.hoist = (two and TOKEN_HOIST and
+                      os.environ.get("GLOM_NO_TOKEN_HOIST", "0") != "1")
+        self.fuse = (two and MIX_FUSION and
+                     os.environ.get("GLOM_NO_MIX_FUSION", "0") != "1")
+        self.bu0 = None
+        self.skip0 = False
+        self.td_in = None
+        self.rnorm = None
+        self.emit = False
+
+    def set_next(self, td_in, rnorm):
+        # the mix returns empty tensors where it does not emit (d != 512)
+        ok = td_in is not None and td_in.numel() > 0
+        self.td_in = td_in if ok else None
+        self.rnorm = rnorm if ok else None
+
+    def tensors(self):
+        return [t for t in (self.bu0, self.td_in, self.rnorm)
+                if t is not None]
 
 
 def level_cone_lo(loss_level_min: int, grad_iters: int, t: int) -> int:
@@ -469,7 +548,7 @@ def _needs_bwd(*tensors):
 
 
 def glom_step(model, tokens, levels, pos, mask, wts=None, slab_ref=None,
-              cone=None):
+              cone=None, carry=None):
     bw = model.bottom_up.net
     tw = model.top_down.net
     if wts is None:
@@ -479,12 +558,22 @@ def glom_step(model, tokens, levels, pos, mask, wts=None, slab_ref=None,
             bw[3].bias,
             tw[1].weight[..., 0], tw[1].bias, tw[3].weight[..., 0],
             tw[3].bias)
+    if carry is not None:
+        # group 0 may be skipped when nothing will read this step's group-0
+        # Hpre / Hact: no backward is recorded, or its cone starts above 0
+        records_bwd = torch.is_grad_enabled() and any(
+            t is not None and t.requires_grad for t in args)
+        carry.skip0 = carry.bu0 is not None and (
+            not records_bwd or (cone is not None and cone[0] >= 1))
     return GlomStepFn.apply(
         *args, model.attention.attend_self, mask, *wts, slab_ref,
-        _needs_bwd(*args), cone)
+        _needs_bwd(*args), cone, carry)
 
 
 _TAIL_STREAM = None
+# what the tail reads besides the slab: held from glom_forward until
+# join_tail_stream (the kept token-MLP output, the last mix's extras)
+_TAIL_KEEP = []
 
 
 def _tail_stream():
@@ -501,6 +590,7 @@ def join_tail_stream():
     trainer joins right before the optimizer update)."""
     if _TAIL_STREAM is not None:
         torch.cuda.current_stream().wait_stream(_TAIL_STREAM)
+    del _TAIL_KEEP[:]
 
 
 def glom_forward(model, img, iters, levels=None, return_all=False,
@@ -564,22 +654,26 @@ def glom_forward(model, img, iters, levels=None, return_all=False,
                and torch.is_grad_enabled())
     n_sync = grad_iters if overlap else iters
 
+    carry = _LoopCarry(levels)
+
     steps = [levels]
     with trace_range(f"glom/iterate x{iters}"):
         for t in range(n_sync):
             sref = (slab, t + 1) if slab is not None else None
+            # the last iteration's mix has no successor to prepare for
+            carry.emit = carry.fuse and t < iters - 1
             with trace_range(f"glom/step{t}"):
                 if grad_iters is not None and t >= grad_iters:
                     with torch.no_grad():
                         levels = glom_step(model, tokens, levels, pos,
-                                           mask, wts, sref)
+                                           mask, wts, sref, None, carry)
                 else:
                     cone = None
                     if loss_level_min is not None:
                         cone = (level_cone_lo(loss_level_min, grad_iters,
                                               t), t)
                     levels = glom_step(model, tokens, levels, pos, mask,
-                                       wts, sref, cone)
+                                       wts, sref, cone, carry)
             if return_all:
                 steps.append(levels)
         if overlap:
@@ -589,18 +683,30 @@ def glom_forward(model, img, iters, levels=None, return_all=False,
             s_tail = _tail_stream()
             ev = torch.cuda.Event()
             ev.record(torch.cuda.current_stream())
+            # the carried tensors were written on the current stream and are
+            # read on s_tail: pin their blocks there, and hold them until
+            # join_tail_stream
+            for kept in carry.tensors():
+                kept.record_stream(s_tail)
+            _TAIL_KEEP[:] = carry.tensors()
             with torch.no_grad(), torch.cuda.stream(s_tail):
                 s_tail.wait_event(ev)
                 for t in range(n_sync, iters):
-                    out8 = ext.glom_step_fwd(
+                    emit = carry.fuse and t < iters - 1
+                    outs = ext.glom_step_fwd(
                         tokens, levels, pos,
                         bw[1].weight[..., 0], bw[1].bias,
                         bw[3].weight[..., 0], bw[3].bias,
                         tw[1].weight[..., 0], tw[1].bias,
                         tw[3].weight[..., 0], tw[3].bias,
                         model.attention.attend_self, mask, slab, t + 1,
-                        FORCE_SAVE_FOR_BWD)
-                    levels = out8[0]
+                        FORCE_SAVE_FOR_BWD, carry.bu0, carry.td_in,
+                        carry.rnorm, emit)
+                    levels = outs[0]
+                    if emit:
+                        carry.set_next(outs[8], outs[9])
+                    else:
+                        carry.set_next(None, None)
                     if return_all:
                         steps.append(levels)
                 if slab is not None:
