@@ -1521,14 +1521,14 @@ torch::Tensor colsum(torch::Tensor x) {
 // global-norm grad clip fused. step_dev is a persistent device counter
 // (incremented on-device so the op is hipGraph-replay-safe).
 
-void fused_adamw(std::vector<torch::Tensor> grads,
-                 std::vector<torch::Tensor> masters,
-                 std::vector<torch::Tensor> m1s,
-                 std::vector<torch::Tensor> m2s,
-                 std::vector<torch::Tensor> params,
-                 double lr, double b1, double b2, double eps, double wd,
-                 double max_norm, torch::Tensor partials, torch::Tensor norm,
-                 torch::Tensor step_dev) {
+static OptTable opt_table(const std::vector<torch::Tensor>& grads,
+                          const std::vector<torch::Tensor>& masters,
+                          const std::vector<torch::Tensor>& m1s,
+                          const std::vector<torch::Tensor>& m2s,
+                          const std::vector<torch::Tensor>& params,
+                          const torch::Tensor& partials,
+                          const torch::Tensor& norm,
+                          const torch::Tensor& step_dev) {
     const size_t nt = grads.size();
     TORCH_CHECK(nt > 0 && nt <= OPT_MAX_T, "fused_adamw: 1..", OPT_MAX_T,
                 " tensors supported, got ", nt);
@@ -1560,6 +1560,19 @@ void fused_adamw(std::vector<torch::Tensor> grads,
         cum += n;
     }
     t.cum[nt] = cum;
+    return t;
+}
+
+void fused_adamw(std::vector<torch::Tensor> grads,
+                 std::vector<torch::Tensor> masters,
+                 std::vector<torch::Tensor> m1s,
+                 std::vector<torch::Tensor> m2s,
+                 std::vector<torch::Tensor> params,
+                 double lr, double b1, double b2, double eps, double wd,
+                 double max_norm, torch::Tensor partials, torch::Tensor norm,
+                 torch::Tensor step_dev) {
+    OptTable t = opt_table(grads, masters, m1s, m2s, params, partials, norm,
+                           step_dev);
     hipStream_t s = cur_stream();
     launch_grad_norm(t, partials.data_ptr<float>(), norm.data_ptr<float>(),
                      step_dev.data_ptr<float>(), s);
@@ -1567,6 +1580,51 @@ void fused_adamw(std::vector<torch::Tensor> grads,
     launch_adamw(t, (float)lr, (float)b1, (float)b2, (float)eps, (float)wd,
                  (float)max_norm, norm.data_ptr<float>(),
                  step_dev.data_ptr<float>(), s);
+    check_launch();
+}
+
+// The scheduled variant: lr comes from the device hyperparameter block
+// `hyper` (layout OPT_H_* in native_ops.h; the finalize kernel evaluates the
+// schedule at the incremented step count and writes this step's lr there),
+// and lr scale / weight decay are per tensor. Same three launches, no sync,
+// no allocation.
+void fused_adamw_sched(std::vector<torch::Tensor> grads,
+                       std::vector<torch::Tensor> masters,
+                       std::vector<torch::Tensor> m1s,
+                       std::vector<torch::Tensor> m2s,
+                       std::vector<torch::Tensor> params,
+                       std::vector<double> lr_scales,
+                       std::vector<double> wds, double b1, double b2,
+                       double eps, double max_norm, torch::Tensor partials,
+                       torch::Tensor norm, torch::Tensor step_dev,
+                       torch::Tensor hyper) {
+    OptTable t = opt_table(grads, masters, m1s, m2s, params, partials, norm,
+                           step_dev);
+    const size_t nt = grads.size();
+    TORCH_CHECK(lr_scales.size() == nt && wds.size() == nt,
+                "fused_adamw_sched: one lr_scale and weight_decay per tensor");
+    TORCH_CHECK(hyper.is_cuda() && hyper.is_contiguous()
+                && hyper.numel() >= OPT_H_SIZE
+                && hyper.scalar_type() == at::kFloat
+                && hyper.device() == step_dev.device(),
+                "fused_adamw_sched: hyper must be ", OPT_H_SIZE,
+                " contiguous fp32 values on the optimizer's device");
+    OptGroups h;
+    std::memset(&h, 0, sizeof(h));
+    for (size_t i = 0; i < nt; i++) {
+        h.lr_scale[i] = (float)lr_scales[i];
+        h.wd[i] = (float)wds[i];
+    }
+    hipStream_t s = cur_stream();
+    launch_grad_norm_sched(t, partials.data_ptr<float>(),
+                           norm.data_ptr<float>(),
+                           step_dev.data_ptr<float>(),
+                           hyper.data_ptr<float>(), s);
+    check_launch();
+    launch_adamw_sched(t, h, (float)b1, (float)b2, (float)eps,
+                       (float)max_norm, norm.data_ptr<float>(),
+                       step_dev.data_ptr<float>(), hyper.data_ptr<float>(),
+                       s);
     check_launch();
 }
 
@@ -1963,6 +2021,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("colsum", &colsum, "fixed-order column sum (M,C) -> (C,)");
     m.def("fused_adamw", &fused_adamw,
           "fused AdamW + global-norm grad clip (torch semantics)");
+    m.def("fused_adamw_sched", &fused_adamw_sched,
+          "fused AdamW with device-resident lr schedule and per-tensor "
+          "lr scale / weight decay");
     m.def("add4_into", &add4_into, "fused 4-way elementwise sum");
     m.def("ff_bwd_dh", &ff_bwd_dh, py::arg("dY"), py::arg("w2t"),
           py::arg("Hpre"), py::arg("g_lo") = 0);

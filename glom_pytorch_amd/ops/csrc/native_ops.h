@@ -59,3 +59,30 @@ void launch_grad_norm(const OptTable& t, float* partials, float* norm,
 void launch_adamw(const OptTable& t, float lr, float b1, float b2, float eps,
                   float wd, float max_norm, const float* norm,
                   const float* step_dev, hipStream_t s);
+
+// ---- scheduled variant: lr lives in device memory ----
+// fp32 hyperparameter block owned by the optimizer (OPT_H_SIZE floats)
+#define OPT_H_BASE_LR 0
+#define OPT_H_KIND 1        // 0 constant, 1 linear decay, 2 cosine decay
+#define OPT_H_WARMUP 2
+#define OPT_H_TOTAL 3
+#define OPT_H_MIN_RATIO 4
+#define OPT_H_LR_T 5        // output: this step's lr, written by finalize
+#define OPT_H_SIZE 8
+
+// per-tensor hyperparameters, indexed like OptTable
+struct OptGroups {
+    float lr_scale[OPT_MAX_T];
+    float wd[OPT_MAX_T];
+};
+
+// launch_grad_norm whose finalize kernel also evaluates the schedule at the
+// incremented step count and writes hyper[OPT_H_LR_T] = base_lr * f(step).
+void launch_grad_norm_sched(const OptTable& t, float* partials, float* norm,
+                            float* step_dev, float* hyper, hipStream_t s);
+// launch_adamw with lr = hyper[OPT_H_LR_T] * lr_scale[ti] and wd[ti] per
+// tensor; same arithmetic, bit-identical for lr_scale == 1 and equal lr.
+void launch_adamw_sched(const OptTable& t, const OptGroups& h, float b1,
+                        float b2, float eps, float max_norm,
+                        const float* norm, const float* step_dev,
+                        const float* hyper, hipStream_t s);

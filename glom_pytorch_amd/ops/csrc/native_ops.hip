@@ -15,6 +15,9 @@
 //   - k_grad_norm_* / k_adamw: fused bf16-grad -> fp32-master AdamW with
 //     global-norm clipping; replaces the per-step Python master-weight
 //     copy loop + foreach-AdamW + copy-back (torch semantics preserved).
+//   - k_grad_norm_fin_sched / k_adamw_sched: the same with the learning
+//     rate in device memory (schedule evaluated from the device step
+//     counter) and per-tensor lr scale / weight decay.
 // All tensor I/O bf16 unless noted; accumulation f32.
 
 #include "common.h"
@@ -415,6 +418,116 @@ __global__ __launch_bounds__(NT256) void k_adamw(
             pw[i] = f2bf(p);
         }
     }
+}
+
+// k_grad_norm_fin plus the learning-rate schedule: the same fixed-order sum
+// and step increment, then thread 0 evaluates the schedule at the 0-based
+// step index s = t - 1 from the device hyperparameter block and leaves
+// hyper[OPT_H_LR_T] = base_lr * f(s) for k_adamw_sched. A pure function of
+// the device counter, so a captured step replays it correctly.
+__global__ __launch_bounds__(NT256) void k_grad_norm_fin_sched(
+        const float* __restrict__ partials, float* __restrict__ norm,
+        float* __restrict__ step_dev, float* __restrict__ hyper) {
+    __shared__ float red[NT256 / WAVE];
+    float acc = 0.f;
+    for (int i = threadIdx.x; i < OPT_NPART; i += NT256) acc += partials[i];
+    acc = wave_reduce_sum(acc);
+    if (threadIdx.x % WAVE == 0) red[threadIdx.x / WAVE] = acc;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        float s = 0.f;
+        for (int w = 0; w < NT256 / WAVE; w++) s += red[w];
+        norm[0] = sqrtf(s);
+        const float tstep = step_dev[0] + 1.0f;
+        step_dev[0] = tstep;
+
+        const float si = tstep - 1.0f;
+        const int kind = (int)hyper[OPT_H_KIND];
+        const float W = hyper[OPT_H_WARMUP];
+        const float T = hyper[OPT_H_TOTAL];
+        const float mr = hyper[OPT_H_MIN_RATIO];
+        float f;
+        if (si < W) {
+            f = (si + 1.0f) / W;
+        } else if (kind == 0) {
+            f = 1.0f;
+        } else if (si >= T) {
+            f = mr;
+        } else {
+            const float x = (si - W) / (T - W);
+            const float shape = kind == 1
+                ? 1.0f - x
+                : 0.5f * (1.0f + cosf(3.14159265358979323846f * x));
+            f = mr + (1.0f - mr) * shape;
+        }
+        hyper[OPT_H_LR_T] = hyper[OPT_H_BASE_LR] * f;
+    }
+}
+
+// k_adamw with lr read from the device block and per-tensor lr scale and
+// weight decay: the same statements in the same fp32 order, so with
+// lr_scale == 1 it reproduces k_adamw's bits for the same fp32 lr.
+__global__ __launch_bounds__(NT256) void k_adamw_sched(
+        OptTable t, OptGroups h, float b1, float b2, float eps,
+        float max_norm, const float* __restrict__ norm,
+        const float* __restrict__ step_dev,
+        const float* __restrict__ hyper) {
+    // k_adamw compiles to separately rounded operations except for decay,
+    // which is one fma. Pin exactly that here, so that moving the
+    // per-tensor values into the loop cannot fuse anything else.
+#pragma clang fp contract(off)
+    const float tstep = step_dev[0];
+    const float lr_t = hyper[OPT_H_LR_T];
+    float scale = 1.0f;
+    if (max_norm > 0.f) {
+        float c = max_norm / (norm[0] + 1e-6f);
+        scale = fminf(1.0f, c);
+    }
+    const float bc1 = 1.0f - __powf(b1, tstep);
+    const float bc2 = 1.0f - __powf(b2, tstep);
+    const float inv_bc2 = 1.0f / bc2;
+
+    long gid = (long)blockIdx.x * NT256 + threadIdx.x;
+    const long gstride = (long)gridDim.x * NT256;
+    for (int ti = 0; ti < t.nt; ti++) {
+        const float lr = lr_t * h.lr_scale[ti];
+        const float wd = h.wd[ti];
+        const float step_size = lr / bc1;
+        const float decay = fmaf(-lr, wd, 1.0f);    // 1 - lr * wd
+        const ushort_t* gp = t.g[ti];
+        float* mw = t.mw[ti];
+        float* m1 = t.m1[ti];
+        float* m2 = t.m2[ti];
+        ushort_t* pw = t.pw[ti];
+        long n = t.cum[ti + 1] - t.cum[ti];
+        for (long i = gid; i < n; i += gstride) {
+            float g = bf2f(gp[i]) * scale;
+            float m = fmaf(b1, m1[i], (1.0f - b1) * g);
+            float v = fmaf(b2, m2[i], (1.0f - b2) * g * g);
+            m1[i] = m;
+            m2[i] = v;
+            float p = mw[i] * decay;
+            p -= step_size * m / (sqrtf(v * inv_bc2) + eps);
+            mw[i] = p;
+            pw[i] = f2bf(p);
+        }
+    }
+}
+
+void launch_grad_norm_sched(const OptTable& t, float* partials, float* norm,
+                            float* step_dev, float* hyper, hipStream_t s) {
+    hipLaunchKernelGGL(k_grad_norm_part, dim3(OPT_NPART), dim3(NT256), 0, s,
+                       t, partials);
+    hipLaunchKernelGGL(k_grad_norm_fin_sched, dim3(1), dim3(NT256), 0, s,
+                       partials, norm, step_dev, hyper);
+}
+
+void launch_adamw_sched(const OptTable& t, const OptGroups& h, float b1,
+                        float b2, float eps, float max_norm,
+                        const float* norm, const float* step_dev,
+                        const float* hyper, hipStream_t s) {
+    hipLaunchKernelGGL(k_adamw_sched, dim3(2048), dim3(NT256), 0, s, t, h,
+                       b1, b2, eps, max_norm, norm, step_dev, hyper);
 }
 
 void launch_grad_norm(const OptTable& t, float* partials, float* norm,

@@ -54,7 +54,8 @@ class DenoisingTrainer:
                  process_group=None, graph_step=True, overlap_tail=True,
                  micro_batches=1, log_path=None, contrast_weight=0.0,
                  contrast_level=-1, contrast_temperature=0.1,
-                 contrast_negatives="other_images", level_cone=True):
+                 contrast_negatives="other_images", level_cone=True,
+                 lr_schedule=None, no_decay=False):
         """``process_group``: the group whose ranks are data-parallel
         replicas (default: the global group). For 2-D DP x SP meshes pass
         the DP subgroup here — BucketedDDP AVERAGES over its group, which
@@ -83,8 +84,32 @@ class DenoisingTrainer:
         (``loss_level_min``: the top level, or ``contrast_level`` when the
         contrastive term is on and lower), so the backward skips the level
         groups whose gradient is exactly zero. Same losses and updates.
-        Disable with level_cone=False or GLOM_NO_LEVEL_CONE=1."""
+        Disable with level_cone=False or GLOM_NO_LEVEL_CONE=1.
+
+        ``lr_schedule`` (default None = constant ``lr``): an
+        ``ops.optim.LRSchedule``; step ``k`` (0-based) runs at
+        ``lr * lr_schedule.factor(k)``. The fused optimizer evaluates it on
+        the device from its step counter (no host sync, no extra launch);
+        the torch-AdamW paths set their groups' lr from the same formula
+        before each step.
+
+        ``no_decay`` (default False = weight decay 1e-2 everywhere): weight
+        decay 0 for every parameter with ``ndim <= 1`` plus
+        ``pos_emb.weight`` and ``init_levels``.
+
+        With a schedule, ``no_decay``, or once ``trainer.opt.lr`` is
+        assigned on the fused path, the step is launched eagerly instead of
+        replayed from the captured graph (whose kernel arguments are
+        frozen): the assignment takes effect on the next step, at the
+        eager-launch step cost. Capturing such steps is not implemented."""
         from glom_pytorch_amd.contrast import NEGATIVES
+        from glom_pytorch_amd.ops.optim import LRSchedule
+        if lr_schedule is not None and not isinstance(lr_schedule,
+                                                      LRSchedule):
+            raise ValueError("lr_schedule must be an LRSchedule or None")
+        self.base_lr = float(lr)
+        self.lr_schedule = lr_schedule
+        self.no_decay = bool(no_decay)
         if contrast_weight < 0 or not contrast_temperature > 0:
             raise ValueError("contrast_weight must be >= 0 and "
                              "contrast_temperature > 0")
@@ -113,6 +138,26 @@ class DenoisingTrainer:
             self.heartbeat = Heartbeat(every_steps=50)
         params = list(model.parameters()) + list(self.decoder.parameters())
         self._params = params
+        names = ([n for n, _ in model.named_parameters()]
+                 + ["decoder." + n
+                    for n, _ in self.decoder.named_parameters()])
+        # per-parameter weight decay: with no_decay, none on biases and
+        # other <=1-D tensors nor on the two embedding tables
+        wds = [0.0 if self.no_decay and (
+                   q.ndim <= 1 or n in ("pos_emb.weight", "init_levels"))
+               else 1e-2 for n, q in zip(names, params)]
+
+        def torch_adamw(tensors):
+            if not self.no_decay:
+                return torch.optim.AdamW(tensors, lr=lr, foreach=True)
+            # groups in order of first appearance, as FusedAdamW
+            # partitions them, so optimizer states interchange
+            groups: dict = {}
+            for t, w in zip(tensors, wds):
+                groups.setdefault(w, []).append(t)
+            return torch.optim.AdamW(
+                [{"params": ts, "weight_decay": w}
+                 for w, ts in groups.items()], lr=lr, foreach=True)
         # bf16 training keeps fp32 master weights: updates of size lr*grad
         # would otherwise partially round away in bf16 parameter storage
         self.master = None
@@ -125,14 +170,15 @@ class DenoisingTrainer:
                 # bf16 params, with the global-norm clip fused
                 from glom_pytorch_amd.ops.optim import FusedAdamW
                 self.fused_opt = FusedAdamW(
-                    params, self.master, lr=lr, weight_decay=1e-2,
-                    max_grad_norm=grad_clip if grad_clip else 0.0)
+                    params, self.master, lr=lr,
+                    weight_decay=wds if self.no_decay else 1e-2,
+                    max_grad_norm=grad_clip if grad_clip else 0.0,
+                    schedule=lr_schedule)
                 self.opt = self.fused_opt
             else:
-                self.opt = torch.optim.AdamW(self.master, lr=lr,
-                                             foreach=True)
+                self.opt = torch_adamw(self.master)
         else:
-            self.opt = torch.optim.AdamW(params, lr=lr, foreach=True)
+            self.opt = torch_adamw(params)
         self.grad_clip = grad_clip
         self.step_idx = 0
         self.log_path = log_path
@@ -168,6 +214,23 @@ class DenoisingTrainer:
         from glom_pytorch_amd import ops
         return ops.available()
 
+    def _torch_opt_step(self):
+        """Step of the torch-AdamW paths (CPU, fp32, no extension). With a
+        schedule, every group first gets ``base * factor(step_idx)``: the
+        specification the fused optimizer evaluates on the device."""
+        if self.lr_schedule is not None:
+            lr = self.base_lr * self.lr_schedule.factor(self.step_idx)
+            for g in self.opt.param_groups:
+                g["lr"] = lr
+        self.opt.step()
+
+    def current_lr(self) -> float:
+        """The learning rate the most recent step used (the base lr before
+        the first). One host sync on the fused path."""
+        if self.fused_opt is not None:
+            return self.fused_opt.current_lr()
+        return float(self.opt.param_groups[0]["lr"])
+
     # ------------------------------ stepping -------------------------- #
 
     def step(self, img: torch.Tensor, iters: int | None = None,
@@ -189,8 +252,13 @@ class DenoisingTrainer:
         # micro-pipelining accumulates grads across streams; the
         # AccumulateGrad node's stream mismatch breaks hipGraph capture
         # (torch warns, replay faults) — micro mode runs eager-launched
+        # a captured step bakes in the optimizer's kernel-argument lr; once
+        # lr lives in device memory (schedule, per-tensor groups, or an lr
+        # assigned after construction) steps are launched eagerly, where it
+        # is live. Capturing those steps is left out for now.
         return (self.graph_step and self.micro_batches == 1
                 and self.fused_opt is not None
+                and not self.fused_opt._uses_device_lr()
                 and img.is_cuda and img.dtype == torch.bfloat16
                 and not getattr(self.model, "force_eager", False)
                 and os.environ.get("GLOM_FORCE_EAGER", "0") != "1")
@@ -237,7 +305,7 @@ class DenoisingTrainer:
                 if self.grad_clip:
                     torch.nn.utils.clip_grad_norm_(self.master,
                                                    self.grad_clip)
-                self.opt.step()
+                self._torch_opt_step()
                 for mw, q in zip(self.master, self._params):
                     q.data.copy_(mw)
         else:
@@ -245,7 +313,7 @@ class DenoisingTrainer:
                 torch.nn.utils.clip_grad_norm_(
                     [q for g in self.opt.param_groups for q in g["params"]],
                     self.grad_clip)
-            self.opt.step()
+            self._torch_opt_step()
         return loss.detach()
 
     def _contrast_step(self, img: torch.Tensor, iters: int) -> torch.Tensor:
@@ -291,7 +359,7 @@ class DenoisingTrainer:
                 if self.grad_clip:
                     torch.nn.utils.clip_grad_norm_(self.master,
                                                    self.grad_clip)
-                self.opt.step()
+                self._torch_opt_step()
                 for mw, q in zip(self.master, self._params):
                     q.data.copy_(mw)
         else:
@@ -299,7 +367,7 @@ class DenoisingTrainer:
                 torch.nn.utils.clip_grad_norm_(
                     [q for g in self.opt.param_groups for q in g["params"]],
                     self.grad_clip)
-            self.opt.step()
+            self._torch_opt_step()
         return loss.detach()
 
     def _micro_forward(self, half: torch.Tensor, iters: int, t: int,
@@ -366,11 +434,11 @@ class DenoisingTrainer:
                 if self.grad_clip:
                     torch.nn.utils.clip_grad_norm_(self.master,
                                                    self.grad_clip)
-                self.opt.step()
+                self._torch_opt_step()
                 for mw, q in zip(self.master, self._params):
                     q.data.copy_(mw)
         else:
-            self.opt.step()
+            self._torch_opt_step()
         return loss.detach()
 
     # --------------------- hipGraph-captured step --------------------- #
@@ -469,6 +537,11 @@ class DenoisingTrainer:
             "optimizer": self.opt.state_dict(),
             "master": self.master,
             "step": self.step_idx,
+            "lr_schedule": (self.lr_schedule.to_dict()
+                            if self.lr_schedule is not None else None),
+            "base_lr": (self.fused_opt.lr if self.fused_opt is not None
+                        else self.base_lr),
+            "no_decay": self.no_decay,
             "rng": torch.get_rng_state(),
             "cuda_rng": (torch.cuda.get_rng_state()
                          if torch.cuda.is_available() else None),
@@ -477,9 +550,26 @@ class DenoisingTrainer:
 
     def load_checkpoint(self, path: str):
         ckpt = torch.load(path, map_location="cpu", weights_only=False)
+        # checkpoints from before schedules existed: constant lr, decay on
+        if bool(ckpt.get("no_decay", False)) != self.no_decay:
+            raise ValueError(
+                f"checkpoint was written with no_decay="
+                f"{bool(ckpt.get('no_decay', False))}, this trainer has "
+                f"no_decay={self.no_decay}")
         self.model.load_state_dict(ckpt["model"])
         self.decoder.load_state_dict(ckpt["decoder"])
         self.opt.load_state_dict(ckpt["optimizer"])
+        if "lr_schedule" in ckpt:
+            # the step count travels in the optimizer state, so the resumed
+            # run continues the schedule where the saved one stopped
+            from glom_pytorch_amd.ops.optim import LRSchedule
+            d = ckpt["lr_schedule"]
+            self.lr_schedule = (LRSchedule.from_dict(d) if d is not None
+                                else None)
+            self.base_lr = float(ckpt["base_lr"])
+            if self.fused_opt is not None:
+                self.fused_opt._lr = self.base_lr
+                self.fused_opt.schedule = self.lr_schedule
         if ckpt.get("master") is not None and self.master is not None:
             for mw, saved in zip(self.master, ckpt["master"]):
                 mw.data.copy_(saved.to(mw.device))
