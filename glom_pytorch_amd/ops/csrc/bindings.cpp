@@ -358,12 +358,17 @@ void run_gemm(GemmParams& p, hipStream_t s, const torch::TensorOptions& opts,
     if (disp_dbg)
         fprintf(stderr,
                 "[dispatch] L%d M%ld N%ld K%ld epi%d nt3=%d nt5p=%d on=%d "
-                "nt8p=%d ctabflag=%d m512=%d tn_tr=%d sk=%d finw=%d\n",
+                "nt8p=%d ctabflag=%d m512=%d tn_tr=%d sk=%d finw=%d "
+                "kern=%s\n",
                 p.layout, (long)p.M, (long)p.N, (long)p.K, p.epilogue,
                 (int)nt3, (int)nt5p, (int)nt5p_on, (int)nt8p,
                 (int)(p.Cflags & OP_TABLE), (int)(p.M % 512 == 0),
                 tn_tr ? (p.splitk > 1 ? g_tn_tr_variant : 1) : 0,
-                p.splitk, g_finish_wide);
+                p.splitk, g_finish_wide,
+                nt8p ? "nt8p" : nt5p ? "nt5p" : nt3 ? "nt4"
+                : nt_fast ? "nt_fast" : tn_tr ? "tn_tr"
+                : tn_fast ? (p.splitk > 1 ? "tn_sk" : "tn_fast")
+                : nn_fast ? "nn_fast" : "generic");
     if (nt8p)
         launch_gemm_nt_fast8p(p, s);
     else if (nt5p)
@@ -1209,6 +1214,50 @@ torch::Tensor gemm_tn(torch::Tensor A, torch::Tensor B) {
     return C;
 }
 
+// Test-only, as gemm_tn: C[g] = A[g] B[g]^T (+ bias[g] per column) for
+// A (G,M,K), B (G,N,K), bias (G,N) through run_gemm's NT dispatch.
+torch::Tensor gemm_nt(torch::Tensor A, torch::Tensor B,
+                      c10::optional<torch::Tensor> bias_opt = c10::nullopt) {
+    CHECK_IN(A); CHECK_IN(B);
+    TORCH_CHECK(A.dim() == 3 && B.dim() == 3 && A.size(0) == B.size(0)
+                && A.size(2) == B.size(2), "A (G,M,K), B (G,N,K)");
+    const int64_t G = A.size(0), M = A.size(1), K = A.size(2),
+                  N = B.size(1);
+    TORCH_CHECK(K % 8 == 0 && N % 8 == 0, "K and N must be /8");
+    auto C = torch::empty({G, M, N}, A.options());
+    GemmParams p = base_params(M, N, K, LAYOUT_NT, G, G, 1.0f);
+    p.A.base = A.data_ptr(); p.A.sin = M * K; p.A.ld = K;
+    p.B.base = B.data_ptr(); p.B.sin = N * K; p.B.ld = K;
+    p.Cbase = C.data_ptr(); p.Csin = M * N; p.Cld = N;
+    if (bias_opt.has_value()) {
+        auto bias = bias_opt.value();
+        CHECK_IN(bias);
+        TORCH_CHECK(bias.dim() == 2 && bias.size(0) == G
+                    && bias.size(1) == N, "bias (G,N)");
+        p.bias_base = bias.data_ptr(); p.bias_sin = N; p.has_bias = 1;
+    }
+    run_gemm(p, cur_stream(), A.options(), true);
+    return C;
+}
+
+// Test-only, as gemm_tn: C[g] = A[g] B[g] for A (G,M,K), B (G,K,N) through
+// run_gemm's NN dispatch.
+torch::Tensor gemm_nn(torch::Tensor A, torch::Tensor B) {
+    CHECK_IN(A); CHECK_IN(B);
+    TORCH_CHECK(A.dim() == 3 && B.dim() == 3 && A.size(0) == B.size(0)
+                && A.size(2) == B.size(1), "A (G,M,K), B (G,K,N)");
+    const int64_t G = A.size(0), M = A.size(1), K = A.size(2),
+                  N = B.size(2);
+    TORCH_CHECK(K % 8 == 0 && N % 8 == 0, "K and N must be /8");
+    auto C = torch::empty({G, M, N}, A.options());
+    GemmParams p = base_params(M, N, K, LAYOUT_NN, G, G, 1.0f);
+    p.A.base = A.data_ptr(); p.A.sin = M * K; p.A.ld = K;
+    p.B.base = B.data_ptr(); p.B.sin = K * N; p.B.ld = N;
+    p.Cbase = C.data_ptr(); p.Csin = M * N; p.Cld = N;
+    run_gemm(p, cur_stream(), A.options(), true);
+    return C;
+}
+
 void add4_into(torch::Tensor a, torch::Tensor b, torch::Tensor c,
                torch::Tensor d, torch::Tensor out) {
     CHECK_IN(a); CHECK_IN(b); CHECK_IN(c); CHECK_IN(d); CHECK_IN(out);
@@ -2046,6 +2095,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("set_finish_wide", &set_finish_wide,
           "toggle the re-blocked split-K finish (A/B, same bits)");
     m.def("gemm_tn", &gemm_tn, "C = A^T B per group (tests / tuning only)");
+    m.def("gemm_nt", &gemm_nt, "C = A B^T + bias per group (tests only)",
+          py::arg("A"), py::arg("B"), py::arg("bias") = c10::nullopt);
+    m.def("gemm_nn", &gemm_nn, "C = A B per group (tests only)");
     m.def("set_wide_epilogue", &set_wide_epilogue,
           "toggle the 16-byte register epilogue of nt5p (A/B)");
     m.def("set_wide_epilogue_mode", &set_wide_epilogue_mode,

@@ -9,6 +9,7 @@
 
 typedef short short8 __attribute__((ext_vector_type(8)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef unsigned int uint4v __attribute__((ext_vector_type(4)));
 
 typedef unsigned short ushort_t;
@@ -33,6 +34,13 @@ __device__ __forceinline__ ushort_t f2bf(float f) {
 // epilogue on gfx950; these are pure fma Horner chains at the full VALU
 // rate. Both use that erf and gelu'(x)-0.5 are odd and saturated outside
 // [-4,4] / [-5,5]: clamp, then x * P((x/X)^2).
+// The erf polynomial overshoots at the clamp (about -1.0004 at -4), which
+// would make gelu(x) = 0.5 x (1 + erf) positive and linear in x for very
+// negative x. gelu(x) = x Phi(x) lies between 0 and x, so the result is
+// clamped to that interval (gelu_clamp: one v_med3_f32), which is clamping
+// the polynomial's value to [-1, 1]: x < 0 never gives a positive result,
+// x <= -8 gives exactly zero and large x gives x. The clamp sits on the
+// result so that every operation before it is the one it was.
 __device__ __forceinline__ float fast_erf(float x) {
     const float C[11] = {
         1.128355365e+00f, -6.011598717e+00f, 2.859643773e+01f,
@@ -47,9 +55,15 @@ __device__ __forceinline__ float fast_erf(float x) {
     return xc * p;
 }
 
+// median of (y, 0, x): y clamped to the interval between 0 and x
+__device__ __forceinline__ float gelu_clamp(float y, float x) {
+    return __builtin_amdgcn_fmed3f(y, 0.0f, x);
+}
+
 // exact-erf GELU, matching nn.GELU() default within bf16 rounding
 __device__ __forceinline__ float gelu_f(float x) {
-    return 0.5f * x * (1.0f + fast_erf(x * 0.70710678118654752440f));
+    return gelu_clamp(
+        0.5f * x * (1.0f + fast_erf(x * 0.70710678118654752440f)), x);
 }
 
 // W-wide GELU: the W independent Horner chains are interleaved so the
@@ -58,27 +72,36 @@ __device__ __forceinline__ float gelu_f(float x) {
 template <int W>
 __device__ __forceinline__ void gelu_f_vec(const float* __restrict__ x,
                                            float* __restrict__ y) {
+    static_assert(W % 2 == 0, "gelu_f_vec works on pairs");
     const float C[11] = {
         1.128355365e+00f, -6.011598717e+00f, 2.859643773e+01f,
         -1.048367491e+02f, 2.930073200e+02f, -6.110858998e+02f,
         9.211419265e+02f, -9.628073236e+02f, 6.565095731e+02f,
         -2.612567565e+02f, 4.586479609e+01f};
-    float xc[W], w[W], p[W];
+    // explicit pairs: the chains stay v_pk_fma_f32 although the scalar
+    // clamp at the end keeps the compiler from pairing them by itself
+    f32x2 xv[W / 2], xc[W / 2], w[W / 2], p[W / 2];
 #pragma unroll
-    for (int e = 0; e < W; e++) {
-        float a = x[e] * 0.70710678118654752440f;
-        a = fminf(fmaxf(a, -4.0f), 4.0f);
+    for (int e = 0; e < W / 2; e++) {
+        xv[e] = f32x2{x[2 * e], x[2 * e + 1]};
+        f32x2 a = xv[e] * 0.70710678118654752440f;
+        a.x = fminf(fmaxf(a.x, -4.0f), 4.0f);
+        a.y = fminf(fmaxf(a.y, -4.0f), 4.0f);
         xc[e] = a;
         w[e] = a * a * 0.0625f;
-        p[e] = C[10];
+        p[e] = f32x2{C[10], C[10]};
     }
 #pragma unroll
     for (int k = 9; k >= 0; k--)
 #pragma unroll
-        for (int e = 0; e < W; e++) p[e] = fmaf(p[e], w[e], C[k]);
+        for (int e = 0; e < W / 2; e++)
+            p[e] = __builtin_elementwise_fma(p[e], w[e], f32x2{C[k], C[k]});
 #pragma unroll
-    for (int e = 0; e < W; e++)
-        y[e] = 0.5f * x[e] * (1.0f + xc[e] * p[e]);
+    for (int e = 0; e < W / 2; e++) {
+        f32x2 r = 0.5f * xv[e] * (1.0f + xc[e] * p[e]);
+        y[2 * e] = gelu_clamp(r.x, xv[e].x);
+        y[2 * e + 1] = gelu_clamp(r.y, xv[e].y);
+    }
 }
 
 template <int W>

@@ -141,6 +141,32 @@ def test_grouped_ff_op():
         err = _rel_err(out_td[..., g, :], y)
         assert err < 1e-2, (g, err)
 
+    # per element, stage by stage: each GEMM against fp64 of the bf16
+    # operands the kernel itself read (x and the returned Hact)
+    from _bounds_util import assert_within, gemm_tol
+    from glom_pytorch_amd.ops import _load_extension
+    ext = _load_extension()
+    M = B * N
+    td_x = [(levels[..., g + 1, :] + pos.view(1, N, d)) for g in range(L - 1)]
+    for mode, args, xin, res in (
+            (0, (tokens, levels, None, w1, b1, w2, b2),
+             [tokens] + [levels[..., g, :] for g in range(L - 1)], out),
+            (1, (None, levels, pos, w1t, b1t, w2t, b2t), td_x, out_td)):
+        Y, Hpre, Hact, _ = ext.grouped_ff_fwd(*args, mode)
+        assert torch.equal(Y, res)
+        W1, B1, W2, B2 = (t.double() for t in args[3:])
+        for g in range(len(xin)):
+            x = xin[g].double().reshape(M, d)
+            wa, ba = W1[g * m4:(g + 1) * m4], B1[g * m4:(g + 1) * m4]
+            h = x @ wa.t() + ba
+            assert_within(Hpre[g], h, gemm_tol(
+                h, x.abs() @ wa.abs().t() + ba.abs(), d), "Hpre")
+            a = Hact[g].double()
+            wb, bb = W2[g * d:(g + 1) * d], B2[g * d:(g + 1) * d]
+            y = a @ wb.t() + bb
+            assert_within(Y[..., g, :].reshape(M, d), y, gemm_tol(
+                y, a.abs() @ wb.abs().t() + bb.abs(), m4), "Y")
+
 
 def test_consensus_op():
     from glom_pytorch_amd.ops.functional import ConsensusFn
@@ -160,6 +186,16 @@ def test_consensus_op():
         ref = torch.einsum("blij,bjld->bild", sim.softmax(-1), lv)
         err = _rel_err(out, ref)
         assert err < 1e-2, (attend_self, err)
+        # per element: the AV product against fp64 of the stored probs
+        from _bounds_util import assert_within, gemm_tol
+        from glom_pytorch_amd.ops import _load_extension
+        out2, probs, _ = _load_extension().consensus_fwd(levels, attend_self,
+                                                         None)
+        assert torch.equal(out2, out)
+        P, x = probs.double(), levels.double().permute(0, 2, 1, 3)
+        o64 = torch.matmul(P, x).permute(0, 2, 1, 3)
+        oabs = torch.matmul(P, x.abs()).permute(0, 2, 1, 3)
+        assert_within(out, o64, gemm_tol(o64, oabs, N), "out")
 
 
 def test_consensus_op_backward():

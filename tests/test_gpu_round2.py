@@ -65,6 +65,30 @@ def test_patch_embed_parity(dim, patch, size, batch):
                          p2=patch)
     assert _rel_err(ig.grad, dimg_ref) < 2e-2
 
+    # per element against fp64 of the same bf16 operands: any-order f32
+    # accumulation over K (padded to a multiple of 64 with zero columns,
+    # which add nothing to |A| @ |B|) plus one bf16 rounding
+    from _bounds_util import assert_within, gemm_tol
+    K0, Kp = patch * patch * 3, (patch * patch * 3 + 63) // 64 * 64
+    x64, w64, b64 = x32.detach().double(), w.double(), b.double()
+    M = x64.shape[0] * x64.shape[1]
+    assert_within(out, x64 @ w64.t() + b64,
+                  gemm_tol(x64 @ w64.t() + b64,
+                           x64.abs() @ w64.abs().t() + b64.abs(), Kp), "out")
+    dy64 = dY.to(torch.bfloat16).double().reshape(M, dim)
+    xf = x64.reshape(M, K0)
+    assert_within(wg.grad, dy64.t() @ xf,
+                  gemm_tol(dy64.t() @ xf, dy64.abs().t() @ xf.abs(), M), "dW")
+    assert_within(bg.grad, dy64.sum(0),
+                  gemm_tol(dy64.sum(0), dy64.abs().sum(0), M), "db")
+    dx64 = (dy64 @ w64).reshape(x64.shape)
+    dxa = (dy64.abs() @ w64.abs()).reshape(x64.shape)
+    back = dict(h=size // patch, w=size // patch, p1=patch, p2=patch)
+    pat = "b (h w) (p1 p2 c) -> b c (h p1) (w p2)"
+    assert_within(ig.grad, rearrange(dx64, pat, **back),
+                  gemm_tol(rearrange(dx64, pat, **back),
+                           rearrange(dxa, pat, **back), dim), "dimg")
+
 
 def test_patch_embed_in_model_trace():
     """The native forward must route K1 through the HIP patch embed (no

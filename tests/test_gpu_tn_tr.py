@@ -97,6 +97,10 @@ def test_gemm_tn_bitwise_and_fp64(M, N, K, G):
     r = _rel(new[0], ref)
     print("gemm_tn", (M, N, K, G), "rel", r)
     assert r < TN_BOUND
+    # and every element within the any-order f32 accumulation bound
+    from _bounds_util import assert_within, gemm_tol
+    absprod = torch.matmul(A.double().abs().transpose(1, 2), B.double().abs())
+    assert_within(new[0], ref, gemm_tol(ref, absprod, K), "gemm_tn")
 
 
 def test_finish_wide_alone_bitwise():
