@@ -1,5 +1,6 @@
-"""Contrastive regularisation of the top level — the reference README's last
-open to-do ("contrastive / consistency regularization of top-ish levels").
+"""Contrastive regularisation of the top level — the contrastive half of the
+reference README's open to-do ("contrastive / consistency regularization of
+top-ish levels"; the consistency half is not built yet).
 Two corruptions of the same images go through the model in one batch; the
 embedding of a patch column at the top level should agree across the two
 views and differ from the columns of other images. On GPU (bf16) the loss

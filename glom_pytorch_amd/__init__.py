@@ -24,6 +24,8 @@ from glom_pytorch_amd.parse import (ParseTree, island_parents, island_means,
                                     parse_tree)
 from glom_pytorch_amd import contrast
 from glom_pytorch_amd.contrast import column_contrastive_loss
+from glom_pytorch_amd import consistency
+from glom_pytorch_amd.consistency import consistency_loss
 
 __version__ = "0.2.0"
 
@@ -31,4 +33,4 @@ __all__ = ["Glom", "GroupedFeedForward", "ConsensusAttention", "islands",
            "edge_agreement", "labels_from_agreement", "island_labels",
            "island_sizes", "island_count", "parse", "ParseTree",
            "island_parents", "island_means", "parse_tree", "contrast",
-           "column_contrastive_loss"]
+           "column_contrastive_loss", "consistency", "consistency_loss"]

@@ -289,8 +289,12 @@ class Glom(nn.Module):
     # compare the HIP engine against it.
 
     def _eager_forward(self, img, iters, levels, return_all,
-                       grad_iters=None, loss_level_min=None):
+                       grad_iters=None, loss_level_min=None,
+                       return_consistency=False):
         # loss_level_min: accepted and ignored (autograd computes the zeros)
+        # return_consistency: also return the (iters, 2, L) consistency
+        # tensor (glom_pytorch_amd.consistency; not yet reachable from
+        # forward(), see docs/ARCHITECTURE.md "Consistency loss")
         b = img.shape[0]
         tokens = self.image_to_tokens(img)
         n = tokens.shape[1]
@@ -303,19 +307,30 @@ class Glom(nn.Module):
             levels = repeat(self.init_levels, "l d -> b n l d", b=b, n=n)
 
         trajectory = [levels]
+        rows = []
+        # the keyword is passed only when the term is asked for: callers
+        # may wrap _eager_step with its three-argument form (the level-cone
+        # CPU test records the steps that way)
+        kw = dict(consistency=True) if return_consistency else {}
         for t in range(iters):
             if grad_iters is not None and t >= grad_iters:
                 with torch.no_grad():
-                    levels = self._eager_step(bottom, levels, pos)
+                    step = self._eager_step(bottom, levels, pos, **kw)
             else:
-                levels = self._eager_step(bottom, levels, pos)
+                step = self._eager_step(bottom, levels, pos, **kw)
+            if return_consistency:
+                levels, row = step
+                rows.append(row)
+            else:
+                levels = step
             trajectory.append(levels)
 
-        if return_all:
-            return torch.stack(trajectory)
-        return levels
+        out = torch.stack(trajectory) if return_all else levels
+        if return_consistency:
+            return out, torch.stack(rows)
+        return out
 
-    def _eager_step(self, bottom, levels, pos):
+    def _eager_step(self, bottom, levels, pos, consistency=False):
         # bottom-up sees [input, level_0 .. level_{L-2}] and predicts levels
         # 0..L-1; top-down sees [level_1 .. level_{L-1}] + pos and predicts
         # levels 0..L-2 (zero for the top slot).
@@ -324,8 +339,19 @@ class Glom(nn.Module):
 
         td_in = levels[..., 1:, :] + pos
         td = self.top_down(td_in)
+        td_pred = td
         td = F.pad(td, (0, 0, 0, 1), value=0.0)
 
         consensus = self.attention(levels)
 
-        return (levels + bu + td + consensus) / self._contrib.to(levels.dtype)
+        new = (levels + bu + td + consensus) / self._contrib.to(levels.dtype)
+        if not consistency:
+            return new
+        # consistency row (2, L): squared distance of each net's prediction
+        # from the (detached) value the column settles on. fp32, or fp64
+        # for an fp64 model
+        ct = torch.promote_types(new.dtype, torch.float32)
+        tgt = new.detach().to(ct)
+        cb = (bu.to(ct) - tgt).pow(2).mean(dim=(0, 1, 3))
+        cd = (td_pred.to(ct) - tgt[..., :-1, :]).pow(2).mean(dim=(0, 1, 3))
+        return new, torch.stack((cb, torch.cat((cd, cd.new_zeros(1)))))
