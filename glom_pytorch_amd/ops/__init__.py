@@ -77,6 +77,26 @@ def set_mix_fusion(on: bool) -> None:
     functional.set_mix_fusion(on)
 
 
+def set_bwd_merge(on: bool) -> None:
+    """Backward merge (default on; ``GLOM_NO_BWD_MERGE=1`` turns it off):
+    under ``loss_level_min`` one cone-aware kernel sums the four
+    levels-gradient contributions of a step and prepares the previous
+    step's mix gradient, the top-down backward reads that gradient in
+    place, dB2 is summed once, and no zero slices are written to be read
+    back; times the loss does not read get no trajectory gradient.
+    Bit-identical either way. Read once per forward."""
+    from glom_pytorch_amd.ops import functional
+    functional.set_bwd_merge(on)
+
+
+def trajectory_at(all_levels, t):
+    """``all_levels[t]`` of a ``return_all`` forward, without the dense
+    trajectory gradient where the forward ran under ``loss_level_min``
+    (see ``ops.functional.trajectory_at``)."""
+    from glom_pytorch_amd.ops import functional
+    return functional.trajectory_at(all_levels, t)
+
+
 def set_check_level_cone(on: bool) -> None:
     """Level-cone check mode: before each step's backward, verify with one
     host sync that the gradient is zero below the level ``loss_level_min``

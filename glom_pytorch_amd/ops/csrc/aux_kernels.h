@@ -30,6 +30,21 @@ void launch_mix_fwd(const void* prev, const void* bu, const void* td,
 bool mix_fwd_can_emit_next(int L, int d);
 void launch_mix_bwd(const void* dout, void* dmix, void* dtd, long total,
                     int L, int d, hipStream_t s);
+// dmix = dout / c_l for levels [lo, L) only; no dtd (d % 8 == 0)
+void launch_mix_bwd_lo(const void* dout, void* dmix, long BN, int L, int d,
+                       int lo, hipStream_t s);
+// Level ranges [x_lo, x_hi) in which the four summands of k_grad_merge are
+// defined; levels below `dead` are written as +0 without a load.
+struct MergeRanges {
+    int a_lo, a_hi, b_lo, b_hi, c_lo, c_hi, d_lo, d_hi, dead;
+};
+// out = bf16(a + b + c + dd) over (B,N,L,d), out-of-range summands +0;
+// dmix_next (optional) = bf16(out / c_l) for levels >= r.dead; posz stores
+// an exact -0 sum as +0 (d % 8 == 0, total = B*N*L*d)
+void launch_grad_merge(const void* a, const void* b, const void* c,
+                       const void* dd, void* out, void* dmix_next,
+                       long total, int L, int d, const MergeRanges& r,
+                       bool posz, hipStream_t s);
 void launch_add4(const void* a, const void* b, const void* c, const void* d,
                  void* out, long total, hipStream_t s);
 void launch_gelu(const void* in, void* out, long total, hipStream_t s);

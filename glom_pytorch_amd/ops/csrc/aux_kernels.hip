@@ -356,6 +356,72 @@ __global__ __launch_bounds__(NTHREADS) void k_mix_bwd(
     if (has_td) *(uint4v*)(dtd + (bn * (L - 1) + l) * (long)d + q) = o.v;
 }
 
+// k_mix_bwd for the levels [lo, L) only, and without the compact dtd copy:
+// the top-down backward reads dmix itself with row stride L*d (backward
+// merge, docs/ARCHITECTURE.md). Levels below lo of dmix are not written.
+__global__ __launch_bounds__(NTHREADS) void k_mix_bwd_lo(
+        const ushort_t* __restrict__ dout, ushort_t* __restrict__ dmix,
+        long live, int L, int d, int lo) {
+    long i8 = ((long)blockIdx.x * NTHREADS + threadIdx.x) * 8;
+    if (i8 >= live) return;
+    const long w = (long)(L - lo) * d;      // live span of one (b,n) row
+    long bn = i8 / w;
+    long r = i8 % w;
+    int l = lo + (int)(r / d);
+    long idx = bn * (long)L * d + (long)lo * d + r;
+    union { uint4v v; ushort_t u[8]; } g, o;
+    g.v = *(const uint4v*)(dout + idx);
+    float c = (l < L - 1) ? 4.0f : 3.0f;
+#pragma unroll
+    for (int e = 0; e < 8; e++) o.u[e] = f2bf(bf2f(g.u[e]) / c);
+    *(uint4v*)(dmix + idx) = o.v;
+}
+
+// Backward merge: the four levels-gradient contributions of one iteration,
+// each defined on a range of level slices only (MergeRanges), summed with
+// k_add4's expression and operand order; a contribution outside its range
+// is not loaded and enters the sum as +0.0f, which is what the zero-filled
+// slices of the unmerged path held. Levels below r.dead get +0 without any
+// load. POSZ: an exact -0 result is stored as +0, as the autograd add of
+// the all-zero trajectory slice made it (bf16(x + 0) == x otherwise).
+// NEXT: also dmix_next = bf16(out / c_l) from the value being stored,
+// k_mix_bwd's expression, for levels >= r.dead (the previous iteration's
+// dmix; nothing reads it below that).
+template <bool NEXT>
+__global__ __launch_bounds__(NTHREADS) void k_grad_merge(
+        const ushort_t* __restrict__ a, const ushort_t* __restrict__ b,
+        const ushort_t* __restrict__ c, const ushort_t* __restrict__ dd,
+        ushort_t* __restrict__ out, ushort_t* __restrict__ dmix_next,
+        long total, int L, int d, MergeRanges r, int posz) {
+    long idx = ((long)blockIdx.x * NTHREADS + threadIdx.x) * 8;
+    if (idx >= total) return;
+    int l = (idx / d) % L;
+    union { uint4v v; ushort_t u[8]; } va, vb, vc, vd, o;
+    const uint4v z = {0, 0, 0, 0};
+    if (l < r.dead) {
+        *(uint4v*)(out + idx) = z;
+        return;
+    }
+    va.v = (l >= r.a_lo && l < r.a_hi) ? *(const uint4v*)(a + idx) : z;
+    vb.v = (l >= r.b_lo && l < r.b_hi) ? *(const uint4v*)(b + idx) : z;
+    vc.v = (l >= r.c_lo && l < r.c_hi) ? *(const uint4v*)(c + idx) : z;
+    vd.v = (l >= r.d_lo && l < r.d_hi) ? *(const uint4v*)(dd + idx) : z;
+#pragma unroll
+    for (int e = 0; e < 8; e++) {
+        ushort_t v = f2bf(bf2f(va.u[e]) + bf2f(vb.u[e]) + bf2f(vc.u[e])
+                          + bf2f(vd.u[e]));
+        if (posz && v == 0x8000) v = 0;
+        o.u[e] = v;
+    }
+    *(uint4v*)(out + idx) = o.v;
+    if (NEXT) {
+        float cl = (l < L - 1) ? 4.0f : 3.0f;
+#pragma unroll
+        for (int e = 0; e < 8; e++) o.u[e] = f2bf(bf2f(o.u[e]) / cl);
+        *(uint4v*)(dmix_next + idx) = o.v;
+    }
+}
+
 // td_in[b,n,g,:] = levels[b,n,g+1,:] + pos[n,:]  for g in 0..L-2
 // (the top-down input of reference glom_pytorch.py:136, materialized once
 // per iteration so the GEMM can stream it with plain 16B loads)
@@ -456,6 +522,35 @@ void launch_mix_bwd(const void* dout, void* dmix, void* dtd, long total,
     hipLaunchKernelGGL(k_mix_bwd, dim3(cdiv(total / 8, NTHREADS)), dim3(NTHREADS),
                        0, s, (const ushort_t*)dout, (ushort_t*)dmix,
                        (ushort_t*)dtd, total, L, d);
+}
+
+void launch_mix_bwd_lo(const void* dout, void* dmix, long BN, int L, int d,
+                       int lo, hipStream_t s) {
+    const long live = BN * (long)(L - lo) * d;
+    if (live <= 0) return;
+    hipLaunchKernelGGL(k_mix_bwd_lo, dim3(cdiv(live / 8, NTHREADS)),
+                       dim3(NTHREADS), 0, s, (const ushort_t*)dout,
+                       (ushort_t*)dmix, live, L, d, lo);
+}
+
+void launch_grad_merge(const void* a, const void* b, const void* c,
+                       const void* dd, void* out, void* dmix_next,
+                       long total, int L, int d, const MergeRanges& r,
+                       bool posz, hipStream_t s) {
+    if (total <= 0) return;
+    dim3 grid(cdiv(total / 8, NTHREADS)), block(NTHREADS);
+    if (dmix_next)
+        hipLaunchKernelGGL(k_grad_merge<true>, grid, block, 0, s,
+                           (const ushort_t*)a, (const ushort_t*)b,
+                           (const ushort_t*)c, (const ushort_t*)dd,
+                           (ushort_t*)out, (ushort_t*)dmix_next, total, L, d,
+                           r, posz ? 1 : 0);
+    else
+        hipLaunchKernelGGL(k_grad_merge<false>, grid, block, 0, s,
+                           (const ushort_t*)a, (const ushort_t*)b,
+                           (const ushort_t*)c, (const ushort_t*)dd,
+                           (ushort_t*)out, (ushort_t*)nullptr, total, L, d,
+                           r, posz ? 1 : 0);
 }
 
 // out = a + b + c + d, elementwise bf16 (the four levels-gradient

@@ -587,7 +587,16 @@ std::vector<torch::Tensor> grouped_ff_bwd(
         c10::optional<torch::Tensor> w1t_opt = c10::nullopt,
         c10::optional<torch::Tensor> w2t_opt = c10::nullopt,
         c10::optional<torch::Tensor> td_in_opt = c10::nullopt,
-        int64_t g_lo = 0) {
+        int64_t g_lo = 0, int64_t dy_ld = 0,
+        c10::optional<torch::Tensor> dB2_ready = c10::nullopt,
+        bool no_fill = false) {
+    // dy_ld (0 = G*d): row stride of dY in elements. The top-down call of
+    // the merged backward passes dmix (B,N,L,d) itself with dy_ld = L*d:
+    // its first L-1 level slices are what the compact dtd copy held.
+    // dB2_ready: the dB2 result, already computed (db2_cone); no column sum
+    // of dY is run. no_fill: the level slices of dLevels that no live group
+    // writes are left unwritten, for a consumer that knows the written
+    // range (grad_merge) instead of reading the zeros back.
     CHECK_IN(dY); CHECK_IN(levels); CHECK_IN(w1); CHECK_IN(w2); CHECK_IN(Hpre);
     CHECK_IN(Hact);
     const int64_t B = levels.size(0), N = levels.size(1),
@@ -596,6 +605,15 @@ std::vector<torch::Tensor> grouped_ff_bwd(
     const int64_t m4 = w1.size(0) / G;
     const int64_t M = B * N;
     TORCH_CHECK(g_lo >= 0 && g_lo <= G, "g_lo out of range");
+    const int64_t ldY = dy_ld > 0 ? dy_ld : G * d;
+    TORCH_CHECK(ldY >= G * d && (dy_ld == 0 || ldY % 8 == 0),
+                "dy_ld must be a multiple of 8 and at least G * d");
+    TORCH_CHECK(M == 0 || dY.numel() >= (M - 1) * ldY + G * d,
+                "dY is smaller than (M, G*d) at row stride dy_ld");
+    if (dB2_ready.has_value()) {
+        CHECK_IN((*dB2_ready));
+        TORCH_CHECK(dB2_ready->numel() == G * d, "dB2_ready must be (G*d,)");
+    }
     // live groups [g_lo, G): Ga of them, the first at element offsets
     // g_lo * (group stride) into every per-group operand
     const int64_t Ga = G - g_lo;
@@ -607,12 +625,14 @@ std::vector<torch::Tensor> grouped_ff_bwd(
     // and those of the dead groups; zero just these instead of a
     // full-tensor fill
     auto dLevels = torch::empty({B, N, L, d}, opts);
-    zero_unwritten_dx(dLevels.data_ptr(), B * N, L, d, mode, g_lo, s);
+    if (!no_fill)
+        zero_unwritten_dx(dLevels.data_ptr(), B * N, L, d, mode, g_lo, s);
     torch::Tensor dTokens;
     auto dW1 = torch::empty({G * m4, d}, opts);
     auto dW2 = torch::empty({G * d, m4}, opts);
     auto dB1 = torch::empty({G * m4}, opts);
-    auto dB2 = torch::empty({G * d}, opts);
+    auto dB2 = dB2_ready.has_value() ? *dB2_ready
+                                     : torch::empty({G * d}, opts);
     zero_fill(dW1.data_ptr(), g_lo * m4 * d * 2, s);
     zero_fill(dW2.data_ptr(), g_lo * d * m4 * 2, s);
     zero_fill(dB1.data_ptr(), g_lo * m4 * 2, s);
@@ -624,7 +644,7 @@ std::vector<torch::Tensor> grouped_ff_bwd(
     }
     if (Ga == 0) {
         // nothing live: the fills are the whole result
-        zero_fill(dB2.data_ptr(), G * d * 2, s);
+        if (!dB2_ready.has_value()) zero_fill(dB2.data_ptr(), G * d * 2, s);
         return {dTokens, dLevels, dW1, dB1, dW2, dB2};
     }
     TORCH_CHECK(Hpre.numel() == G * M * m4 && Hact.numel() == G * M * m4,
@@ -663,7 +683,7 @@ std::vector<torch::Tensor> grouped_ff_bwd(
     torch::Tensor db1f;
     {
         GemmParams p = base_params(M, m4, d, LAYOUT_NT, Ga, Ga, 1.0f);
-        p.A.base = u16_at(dY, g_lo * d); p.A.sin = d; p.A.ld = G * d;
+        p.A.base = u16_at(dY, g_lo * d); p.A.sin = d; p.A.ld = ldY;
         p.B.base = u16_at(w2t, g_lo * m4 * d); p.B.sin = m4 * d; p.B.ld = d;
         p.Cbase = u16_at(dHpre, g_lo * M * m4); p.Csin = M * m4; p.Cld = m4;
         p.epilogue = EPI_GELUGRAD;
@@ -718,7 +738,7 @@ std::vector<torch::Tensor> grouped_ff_bwd(
     // dW2_g[o, h] = sum_m dY_g[m, o] * Hact_g[m, h]
     {
         GemmParams p = base_params(d, m4, M, LAYOUT_TN, Ga, Ga, 1.0f);
-        p.A.base = u16_at(dY, g_lo * d); p.A.sin = d; p.A.ld = G * d;
+        p.A.base = u16_at(dY, g_lo * d); p.A.sin = d; p.A.ld = ldY;
         p.B.base = u16_at(Hact, g_lo * M * m4); p.B.sin = M * m4; p.B.ld = m4;
         p.Cbase = u16_at(dW2, g_lo * d * m4); p.Csin = d * m4; p.Cld = m4;
         run_gemm(p, s, opts, true, G);
@@ -737,11 +757,16 @@ std::vector<torch::Tensor> grouped_ff_bwd(
     }
     // dB2 = colsum over the M token rows of dY viewed as (M, G*d); the
     // dead groups' columns of dY are zero and sum to zero
-    {
+    if (!dB2_ready.has_value()) {
         auto ws = torch::empty({(long)colsum_rb(M) * G * d},
                                opts.dtype(at::kFloat));
-        launch_colsum(dY.data_ptr(), ws.data_ptr<float>(), dB2.data_ptr(),
-                      1, M, G * d, s);
+        if (ldY == G * d)
+            launch_colsum(dY.data_ptr(), ws.data_ptr<float>(),
+                          dB2.data_ptr(), 1, M, G * d, s);
+        else    // same chains over the row-strided matrix
+            launch_colsum_cone(dY.data_ptr(), ws.data_ptr<float>(),
+                               dB2.data_ptr(), nullptr, M, G * d, 0, ldY, 0,
+                               s);
         check_launch();
     }
     return {dTokens, dLevels, dW1, dB1, dW2, dB2};
@@ -849,7 +874,9 @@ torch::Tensor consensus_bwd(torch::Tensor dOut, torch::Tensor levels,
                             torch::Tensor probs, torch::Tensor rnorm,
                             bool attend_self,
                             c10::optional<torch::Tensor> mask_opt,
-                            int64_t l_lo = 0) {
+                            int64_t l_lo = 0, bool no_fill = false) {
+    // no_fill: levels < l_lo of the result are left unwritten (see
+    // grouped_ff_bwd)
     CHECK_IN(dOut); CHECK_IN(levels); CHECK_IN(probs);
     const int64_t B = levels.size(0), N = levels.size(1),
                   L = levels.size(2), d = levels.size(3);
@@ -864,9 +891,11 @@ torch::Tensor consensus_bwd(torch::Tensor dOut, torch::Tensor levels,
     if (mask_opt.has_value()) mask = mask_opt.value().data_ptr<bool>();
 
     auto dLevels = torch::empty({B, N, L, d}, opts);
-    launch_zero_slices(dLevels.data_ptr(), B * N, (int)L, (int)d, 0,
-                       (int)l_lo, s);
-    check_launch();
+    if (!no_fill) {
+        launch_zero_slices(dLevels.data_ptr(), B * N, (int)L, (int)d, 0,
+                           (int)l_lo, s);
+        check_launch();
+    }
     if (Ll == 0) return dLevels;
     TORCH_CHECK(l_lo == 0 || d % 8 == 0, "l_lo needs dim % 8 == 0");
     const float* rn = rnorm.data_ptr<float>();
@@ -1043,12 +1072,23 @@ torch::Tensor level_mix_fwd(torch::Tensor levels, torch::Tensor bu,
                               c10::nullopt)[0];
 }
 
-std::vector<torch::Tensor> level_mix_bwd(torch::Tensor dout) {
+// want_dtd = false (backward merge): dmix for the levels >= lo only, the
+// rest left unwritten, and no compact dtd (returned empty)
+std::vector<torch::Tensor> level_mix_bwd(torch::Tensor dout, int64_t lo = 0,
+                                         bool want_dtd = true) {
     CHECK_IN(dout);
     const int64_t B = dout.size(0), N = dout.size(1), L = dout.size(2),
                   d = dout.size(3);
     TORCH_CHECK(d % 8 == 0, "dim must be a multiple of 8");
+    TORCH_CHECK(lo >= 0 && lo <= L && (want_dtd ? lo == 0 : true),
+                "lo out of range (and needs want_dtd = false)");
     auto dmix = torch::empty_like(dout);
+    if (!want_dtd) {
+        launch_mix_bwd_lo(dout.data_ptr(), dmix.data_ptr(), B * N, (int)L,
+                          (int)d, (int)lo, cur_stream());
+        check_launch();
+        return {dmix, torch::empty({0}, dout.options())};
+    }
     auto dtd = torch::empty({B, N, L - 1, d}, dout.options());
     launch_mix_bwd(dout.data_ptr(), dmix.data_ptr(), dtd.data_ptr(),
                    dout.numel(), (int)L, (int)d, cur_stream());
@@ -1266,6 +1306,65 @@ void add4_into(torch::Tensor a, torch::Tensor b, torch::Tensor c,
     check_launch();
 }
 
+
+// Backward merge (docs/ARCHITECTURE.md): dLevels of a step whose first
+// live level is `lo`, from the four contributions in the ranges where the
+// no_fill ops wrote them:
+//   dmix, dAttn [lo, L)   bottom-up [max(lo,1)-1, L-1)   top-down [lo+1, L)
+// posz: store an exact -0 as +0 (what the autograd add of the all-zero
+// trajectory slice did on forwards that return the trajectory). next: also
+// return dmix of the previous iteration, bf16(dLevels / c_l), written for
+// levels >= max(lo-1, 0) only (else an empty tensor).
+std::vector<torch::Tensor> grad_merge(torch::Tensor dmix, torch::Tensor bu_dl,
+                                      torch::Tensor td_dl,
+                                      torch::Tensor dattn, int64_t lo,
+                                      bool posz, bool next) {
+    CHECK_IN(dmix); CHECK_IN(bu_dl); CHECK_IN(td_dl); CHECK_IN(dattn);
+    TORCH_CHECK(dmix.dim() == 4, "grad_merge expects (B,N,L,d)");
+    const int64_t L = dmix.size(2), d = dmix.size(3);
+    TORCH_CHECK(d % 8 == 0, "dim must be a multiple of 8");
+    TORCH_CHECK(lo >= 0 && lo <= L, "lo out of range");
+    TORCH_CHECK(bu_dl.sizes() == dmix.sizes() && td_dl.sizes() == dmix.sizes()
+                && dattn.sizes() == dmix.sizes(),
+                "grad_merge: the four contributions must share one shape");
+    MergeRanges r;
+    r.a_lo = (int)lo; r.a_hi = (int)L;
+    r.b_lo = (int)std::max<int64_t>(lo, 1) - 1; r.b_hi = (int)L - 1;
+    r.c_lo = (int)lo + 1; r.c_hi = (int)L;
+    r.d_lo = (int)lo; r.d_hi = (int)L;
+    r.dead = (int)std::max<int64_t>(lo - 1, 0);
+    auto out = torch::empty_like(dmix);
+    auto nxt = next ? torch::empty_like(dmix)
+                    : torch::empty({0}, dmix.options());
+    launch_grad_merge(dmix.data_ptr(), bu_dl.data_ptr(), td_dl.data_ptr(),
+                      dattn.data_ptr(), out.data_ptr(),
+                      next ? nxt.data_ptr() : nullptr, out.numel(), (int)L,
+                      (int)d, r, posz, cur_stream());
+    check_launch();
+    return {out, nxt};
+}
+
+// Both FF nets' dB2 of one step from dmix (B,N,L,d), first live level lo:
+// the column sum over the B*N rows of the columns [lo*d, L*d), +0 below.
+// Returns {(L*d,) bottom-up, ((L-1)*d,) top-down}; the second is the first
+// without the top level (same summands, same order).
+std::vector<torch::Tensor> db2_cone(torch::Tensor dmix, int64_t lo) {
+    CHECK_IN(dmix);
+    TORCH_CHECK(dmix.dim() == 4, "db2_cone expects (B,N,L,d)");
+    const int64_t M = dmix.size(0) * dmix.size(1), L = dmix.size(2),
+                  d = dmix.size(3);
+    TORCH_CHECK(d % 8 == 0, "dim must be a multiple of 8");
+    TORCH_CHECK(lo >= 0 && lo <= L && M > 0, "lo out of range");
+    auto bu = torch::empty({L * d}, dmix.options());
+    auto td = torch::empty({(L - 1) * d}, dmix.options());
+    auto ws = torch::empty({(long)colsum_rb(M) * L * d},
+                           dmix.options().dtype(at::kFloat));
+    launch_colsum_cone(dmix.data_ptr(), ws.data_ptr<float>(), bu.data_ptr(),
+                       L > 1 ? td.data_ptr() : nullptr, M, L * d,
+                       (L - 1) * d, L * d, lo * d, cur_stream());
+    check_launch();
+    return {bu, td};
+}
 
 // ------------------------------------------------------------------ //
 // Fine-grained FF backward stages (stream-forked by the python layer):
@@ -1534,17 +1633,24 @@ std::vector<torch::Tensor> patch_embed_bwd(torch::Tensor dTokens,
     return {dW, dB, dImg};
 }
 
-torch::Tensor dpos(torch::Tensor dLevels) {
+// l0 (default 1): first level summed; the caller knows the slices below it
+// to be exact zeros (or unwritten). l0 >= L: nothing live, dPos = 0.
+torch::Tensor dpos(torch::Tensor dLevels, int64_t l0 = 1) {
     CHECK_IN(dLevels);
     const int64_t B = dLevels.size(0), N = dLevels.size(1),
                   L = dLevels.size(2), d = dLevels.size(3);
+    TORCH_CHECK(l0 >= 1, "l0 must be at least 1");
     auto out = torch::empty({N, d}, dLevels.options());
+    if (l0 >= L) {
+        zero_fill(out.data_ptr(), N * d * 2, cur_stream());
+        return out;
+    }
     const int BCH = (int)std::min<int64_t>(B, 8);
     auto ws = torch::empty({BCH * N * d},
                            dLevels.options().dtype(at::kFloat));
     launch_dpos(dLevels.data_ptr(), out.data_ptr(),
                 d % 8 == 0 ? ws.data_ptr<float>() : nullptr, BCH,
-                (int)B, (int)N, (int)L, (int)d, cur_stream());
+                (int)B, (int)N, (int)L, (int)d, cur_stream(), (int)l0);
     check_launch();
     return out;
 }
@@ -2027,14 +2133,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("Hpre"), py::arg("Hact"), py::arg("mode"),
           py::arg("w1t") = c10::nullopt,
           py::arg("w2t") = c10::nullopt,
-          py::arg("td_in") = c10::nullopt, py::arg("g_lo") = 0);
+          py::arg("td_in") = c10::nullopt, py::arg("g_lo") = 0,
+          py::arg("dy_ld") = 0, py::arg("dB2_ready") = c10::nullopt,
+          py::arg("no_fill") = false);
     m.def("consensus_fwd", &consensus_fwd, "consensus attention forward",
           py::arg("levels"), py::arg("attend_self"), py::arg("mask"),
           py::arg("rnorm") = c10::nullopt);
     m.def("consensus_bwd", &consensus_bwd, "consensus attention backward",
           py::arg("dOut"), py::arg("levels"), py::arg("probs"),
           py::arg("rnorm"), py::arg("attend_self"), py::arg("mask"),
-          py::arg("l_lo") = 0);
+          py::arg("l_lo") = 0, py::arg("no_fill") = false);
     m.def("level_mix_fwd", &level_mix_fwd, "level mix forward",
           py::arg("levels"), py::arg("bu"), py::arg("td"), py::arg("cons"),
           py::arg("slab") = c10::nullopt, py::arg("slab_idx") = 0,
@@ -2044,7 +2152,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("levels"), py::arg("bu"), py::arg("td"), py::arg("cons"),
           py::arg("slab") = c10::nullopt, py::arg("slab_idx") = 0,
           py::arg("bu0") = c10::nullopt, py::arg("pos") = c10::nullopt);
-    m.def("level_mix_bwd", &level_mix_bwd, "level mix backward");
+    m.def("level_mix_bwd", &level_mix_bwd, "level mix backward",
+          py::arg("dout"), py::arg("lo") = 0, py::arg("want_dtd") = true);
+    m.def("grad_merge", &grad_merge,
+          "cone-aware sum of the four levels-gradient contributions",
+          py::arg("dmix"), py::arg("bu_dl"), py::arg("td_dl"),
+          py::arg("dattn"), py::arg("lo"), py::arg("posz"),
+          py::arg("next"));
+    m.def("db2_cone", &db2_cone, "dB2 of both FF nets from dmix",
+          py::arg("dmix"), py::arg("lo") = 0);
     m.def("glom_step_fwd", &glom_step_fwd, "full GLOM iteration forward",
           py::arg("tokens"), py::arg("levels"), py::arg("pos"),
           py::arg("bw1"), py::arg("bb1"), py::arg("bw2"), py::arg("bb2"),
@@ -2066,7 +2182,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("patch_embed_fwd", &patch_embed_fwd,
           "patchify + embed GEMM (K1)");
     m.def("patch_embed_bwd", &patch_embed_bwd, "patch embed backward");
-    m.def("dpos", &dpos, "positional embedding gradient reduction");
+    m.def("dpos", &dpos, "positional embedding gradient reduction",
+          py::arg("dLevels"), py::arg("l0") = 1);
     m.def("colsum", &colsum, "fixed-order column sum (M,C) -> (C,)");
     m.def("fused_adamw", &fused_adamw,
           "fused AdamW + global-norm grad clip (torch semantics)");

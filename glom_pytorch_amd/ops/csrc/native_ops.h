@@ -22,11 +22,17 @@ void launch_colsum(const void* in, float* partials, void* out, int nprob,
 // fixed order (for partials written by a GEMM's fused-colsum epilogue).
 void launch_colsum_fin(const float* partials, void* out, int nprob, long C,
                        int RB, hipStream_t s);
-// dLevels (B,N,L,d) -> dPos (N,d) = sum over b and l in [1,L).
+// in (M, C) bf16 with row stride ld: out (C,) = column sums of the columns
+// [c_lo, C) in launch_colsum's order and bits, +0 below c_lo; out2
+// (optional) = a copy of out[:C2]. partials: (colsum_rb(M), C) f32.
+void launch_colsum_cone(const void* in, float* partials, void* out,
+                        void* out2, long M, long C, long C2, long ld,
+                        long c_lo, hipStream_t s);
+// dLevels (B,N,L,d) -> dPos (N,d) = sum over b and l in [l0,L), l0 < L.
 // partials: caller-provided (BCH, N, d) f32 workspace (BCH batch chunks);
 // pass nullptr/0 for the scalar single-stage fallback.
 void launch_dpos(const void* dlev, void* out, float* partials, int BCH,
-                 int B, int N, int L, int d, hipStream_t s);
+                 int B, int N, int L, int d, hipStream_t s, int l0 = 1);
 // zero the single level slice out[:, :, l0, :] of a (B,N,L,d) tensor
 void launch_zero_slice(void* out, long BN, int L, int d, int l0,
                        hipStream_t s);

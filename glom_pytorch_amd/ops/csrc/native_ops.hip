@@ -213,16 +213,86 @@ void launch_colsum_fin(const float* partials, void* out, int nprob, long C,
                        dim3(CSF_NT), 0, s, partials, (ushort_t*)out, C, RB);
 }
 
+// Column sum of the columns [c_lo, C) of a row-strided (M, C) matrix (row
+// stride ld >= C elements), the dB2 of a step whose level cone leaves the
+// columns below c_lo exactly zero (backward merge). Same row chunks, same
+// per-column f32 chains in the same order as k_colsum_part / k_colsum_fin,
+// so the live columns get the bits those give; a dead column's chain would
+// have been +0 + 0 + ... and is stored as +0. out2 (optional) receives a
+// second copy of the first C2 columns: the top-down net's dB2, which is the
+// bottom-up one without the top level. c_lo, C, ld % 8 == 0.
+__global__ __launch_bounds__(NT256) void k_colsum_part_cone(
+        const ushort_t* __restrict__ in, float* __restrict__ partials,
+        long M, long C, long ld, long c_lo, int RB) {
+    int rc = blockIdx.y;
+    long chunk = cdivl(M, RB);
+    long r0 = rc * chunk, r1 = min((long)M, r0 + chunk);
+    float* pout = partials + (long)rc * C;
+    long c8 = c_lo + ((long)blockIdx.x * NT256 + threadIdx.x) * 8;
+    if (c8 >= C) return;
+    float acc[8] = {};
+    for (long r = r0; r < r1; r++) {
+        union { uint4v v; ushort_t u[8]; } t;
+        t.v = *(const uint4v*)(in + r * ld + c8);
+#pragma unroll
+        for (int e = 0; e < 8; e++) acc[e] += bf2f(t.u[e]);
+    }
+#pragma unroll
+    for (int e = 0; e < 8; e++) pout[c8 + e] = acc[e];
+}
+
+__global__ __launch_bounds__(CSF_NT) void k_colsum_fin_cone(
+        const float* __restrict__ partials, ushort_t* __restrict__ out,
+        ushort_t* __restrict__ out2, long C, long C2, long c_lo, int RB) {
+    long c = (long)blockIdx.x * CSF_NT + threadIdx.x;
+    if (c >= C) return;
+    ushort_t v = 0;
+    if (c >= c_lo) {
+        const float* base = partials + c;
+        float acc = 0.f;
+        int rc = 0;
+        for (; rc + CSF_UNROLL <= RB; rc += CSF_UNROLL) {
+            float t[CSF_UNROLL];
+#pragma unroll
+            for (int u = 0; u < CSF_UNROLL; u++)
+                t[u] = base[(long)(rc + u) * C];
+#pragma unroll
+            for (int u = 0; u < CSF_UNROLL; u++) acc += t[u];
+        }
+        for (; rc < RB; rc++) acc += base[(long)rc * C];
+        v = f2bf(acc);
+    }
+    out[c] = v;
+    if (out2 && c < C2) out2[c] = v;
+}
+
+void launch_colsum_cone(const void* in, float* partials, void* out,
+                        void* out2, long M, long C, long C2, long ld,
+                        long c_lo, hipStream_t s) {
+    int RB = colsum_rb(M);
+    if (c_lo < C)
+        hipLaunchKernelGGL(k_colsum_part_cone,
+                           dim3(cdivl((C - c_lo) / 8, NT256), RB),
+                           dim3(NT256), 0, s, (const ushort_t*)in, partials,
+                           M, C, ld, c_lo, RB);
+    hipLaunchKernelGGL(k_colsum_fin_cone, dim3(cdivl(C, CSF_NT)),
+                       dim3(CSF_NT), 0, s, partials, (ushort_t*)out,
+                       (ushort_t*)out2, C, C2, c_lo, RB);
+}
+
 // --------------------------------------------------------------------- //
 // positional-embedding gradient: dPos[n, q] = sum_b sum_{l=1..L-1}
 // dLevels[b, n, l, q]  (deterministic: fixed b-then-l order per thread)
+// l0 (default 1): first level summed. With a level cone the slices below
+// td_lo + 1 are exact zeros, and a skipped zero summand leaves an f32 chain
+// that starts at +0 unchanged, so the caller passes l0 = td_lo + 1.
 
 // two-stage when B is large: stage A sums a batch chunk into f32
 // partials (grid.z = BCH chunks -> fills the chip), stage B folds the
 // chunks and writes bf16. d % 8 == 0 on every native config.
 __global__ __launch_bounds__(NT256) void k_dpos_part(
         const ushort_t* __restrict__ dlev, float* __restrict__ partials,
-        int B, int N, int L, int d, int BCH) {
+        int B, int N, int L, int d, int BCH, int l0) {
     long q8 = ((long)blockIdx.x * NT256 + threadIdx.x) * 8;
     int n = blockIdx.y;
     int bc = blockIdx.z;
@@ -231,10 +301,10 @@ __global__ __launch_bounds__(NT256) void k_dpos_part(
     int b0 = bc * bchunk, b1 = min(B, b0 + bchunk);
     float acc[8] = {};
     const long bstride = (long)N * L * d;
-    const ushort_t* base = dlev + ((long)n * L + 1) * d + q8;
+    const ushort_t* base = dlev + ((long)n * L + l0) * d + q8;
     for (int b = b0; b < b1; b++) {
         const ushort_t* p = base + b * bstride;
-        for (int l = 0; l < L - 1; l++) {
+        for (int l = 0; l < L - l0; l++) {
             union { uint4v v; ushort_t u[8]; } t;
             t.v = *(const uint4v*)(p + (long)l * d);
 #pragma unroll
@@ -259,34 +329,35 @@ __global__ __launch_bounds__(NT256) void k_dpos_fin(
 // scalar fallback for d % 8 != 0 (not reachable from the native path)
 __global__ __launch_bounds__(NT256) void k_dpos(
         const ushort_t* __restrict__ dlev, ushort_t* __restrict__ out,
-        int B, int N, int L, int d) {
+        int B, int N, int L, int d, int l0) {
     int q = blockIdx.x * NT256 + threadIdx.x;
     int n = blockIdx.y;
     if (q >= d) return;
     float acc = 0.f;
     const long bstride = (long)N * L * d;
-    const ushort_t* base = dlev + ((long)n * L + 1) * d + q;
+    const ushort_t* base = dlev + ((long)n * L + l0) * d + q;
     for (int b = 0; b < B; b++) {
         const ushort_t* p = base + b * bstride;
-        for (int l = 0; l < L - 1; l++) acc += bf2f(p[(long)l * d]);
+        for (int l = 0; l < L - l0; l++) acc += bf2f(p[(long)l * d]);
     }
     out[(long)n * d + q] = f2bf(acc);
 }
 
 void launch_dpos(const void* dlev, void* out, float* partials, int BCH,
-                 int B, int N, int L, int d, hipStream_t s) {
+                 int B, int N, int L, int d, hipStream_t s, int l0) {
     if (d % 8 == 0 && partials != nullptr && BCH > 0) {
         hipLaunchKernelGGL(k_dpos_part,
                            dim3(cdivl(d / 8, NT256), N, BCH), dim3(NT256),
                            0, s, (const ushort_t*)dlev, partials, B, N, L,
-                           d, BCH);
+                           d, BCH, l0);
         hipLaunchKernelGGL(k_dpos_fin,
                            dim3(cdivl((long)N * d, NT256)), dim3(NT256), 0,
                            s, partials, (ushort_t*)out, (long)N * d, BCH);
         return;
     }
     hipLaunchKernelGGL(k_dpos, dim3(cdivl(d, NT256), N), dim3(NT256), 0, s,
-                       (const ushort_t*)dlev, (ushort_t*)out, B, N, L, d);
+                       (const ushort_t*)dlev, (ushort_t*)out, B, N, L, d,
+                       l0);
 }
 
 // --------------------------------------------------------------------- //

@@ -117,6 +117,36 @@ class TrajectoryFn(torch.autograd.Function):
         return (None,) + tuple(dtraj[t] for t in range(dtraj.shape[0]))
 
 
+class ConeTrajectoryFn(torch.autograd.Function):
+    """TrajectoryFn under the loss_level_min promise (backward merge on):
+    the loss reads time ``t`` only, so only that step's output is an input
+    and every other time gets no gradient at all, instead of an all-zero
+    slice that autograd would add to the gradient coming from the next
+    step."""
+
+    @staticmethod
+    def forward(ctx, slab, step, t):
+        ctx.t = t
+        return slab
+
+    @staticmethod
+    def backward(ctx, dtraj):
+        return None, dtraj[ctx.t], None
+
+
+def trajectory_at(all_levels, t):
+    """``all_levels[t]`` of a ``return_all`` forward. Where the forward ran
+    with ``loss_level_min`` and the backward merge on, this is the step
+    output itself (an alias of the slab's slice that carries the step's
+    ``grad_fn``), so the backward of a later ``[:, :, level]`` select fills
+    one time slice instead of the whole trajectory. Plain indexing keeps
+    working and gives the same values and gradients."""
+    steps = getattr(all_levels, "_glom_steps", None)
+    if steps is None:
+        return all_levels[t]
+    return steps[t % len(steps)]
+
+
 class GroupedFFFn(torch.autograd.Function):
     """Grouped per-level MLP (d -> 4d -> GELU -> d), bottom-up or top-down.
 
@@ -294,10 +324,82 @@ class GlomStepFn(torch.autograd.Function):
                               bw1t, bw2t, tw1t, tw2t, tdin)
         ctx.attend_self = attend_self
         ctx.cone = cone
+        ctx.bwd = carry.bwd if carry is not None and cone is not None \
+            else None
         return out
 
     @staticmethod
+    def _backward_merged(ctx, dnew):
+        """The 3-way fork under a level cone with the backward merge on
+        (docs/ARCHITECTURE.md "Backward merge"): dmix comes from the next
+        step's merge kernel when autograd hands that step's dLevels through
+        untouched; the top-down chain reads dmix with row stride L*d; dB2 is
+        summed once; no chain zero-fills what it does not write, because
+        grad_merge knows each contribution's range."""
+        ext = _load_extension()
+        (tokens, levels, pos, bw1, bw2, tw1, tw2, bhp, bha, thp, tha,
+         probs, rnorm, mask, bw1t, bw2t, tw1t, tw2t,
+         tdin) = ctx.saved_tensors
+        L, d = levels.size(2), levels.size(3)
+        lo, t = ctx.cone
+        if lo > 0 and CHECK_LEVEL_CONE:
+            _check_cone(dnew, lo, t)
+        td_live = lo < L - 1
+        cur = torch.cuda.current_stream()
+        s_td, s_at, _ = GlomStepFn._side_streams()
+        dmix = ctx.bwd.take(dnew, lo)
+        if dmix is None:
+            dmix = ext.level_mix_bwd(dnew.contiguous(), lo, False)[0]
+        ev = torch.cuda.Event()
+        ev.record(cur)
+        # the attention chain is the shortest of the three: it also carries
+        # the one dB2 column sum that both FF nets share
+        with torch.cuda.stream(s_at):
+            s_at.wait_event(ev)
+            dAttn = ext.consensus_bwd(dmix, levels, probs, rnorm,
+                                      ctx.attend_self, mask, lo, True)
+            db2_bu, db2_td = ext.db2_cone(dmix, lo)
+        dmix.record_stream(s_at)
+        bu = ext.grouped_ff_bwd(dmix, tokens, levels, None, bw1, bw2,
+                                bhp, bha, 0, bw1t, bw2t, None, lo, 0,
+                                db2_bu, True)
+        if td_live:
+            with torch.cuda.stream(s_td):
+                s_td.wait_event(ev)
+                td = ext.grouped_ff_bwd(dmix, None, levels, pos, tw1, tw2,
+                                        thp, tha, 1, tw1t, tw2t, tdin, lo,
+                                        L * d, db2_td, True)
+                dPos = ext.dpos(td[1], lo + 1)
+            dmix.record_stream(s_td)
+            cur.wait_stream(s_td)
+        else:
+            # no live top-down group: zero fills of the weight gradients
+            td = ext.grouped_ff_bwd(dmix, None, levels, pos, tw1, tw2,
+                                    thp, tha, 1, tw1t, tw2t, tdin, lo,
+                                    L * d, db2_td, True)
+            dPos = ext.dpos(td[1], L)
+        cur.wait_stream(s_at)
+        back = [dAttn, db2_bu, db2_td]
+        if td_live:
+            back += list(td) + [dPos]
+        for x in back:
+            if x is not None and x.numel():
+                x.record_stream(cur)
+        want_next = t > 0
+        dLevels, dmix_next = ext.grad_merge(dmix, bu[1], td[1], dAttn, lo,
+                                            ctx.bwd.posz, want_next)
+        if want_next:
+            ctx.bwd.put(dLevels, dmix_next, max(lo - 1, 0))
+        return (bu[0], dLevels, dPos, bu[2], bu[3], bu[4], bu[5],
+                td[2], td[3], td[4], td[5], None, None, None, None,
+                None, None, None, None, None, None)
+
+    @staticmethod
     def backward(ctx, dnew):
+        if (ctx.bwd is not None
+                and os.environ.get("GLOM_NO_BWD_STREAMS", "0") != "1"
+                and os.environ.get("GLOM_BWD_FORK", "3") == "3"):
+            return GlomStepFn._backward_merged(ctx, dnew)
         ext = _load_extension()
         (tokens, levels, pos, bw1, bw2, tw1, tw2, bhp, bha, thp, tha,
          probs, rnorm, mask, bw1t, bw2t, tw1t, tw2t,
@@ -479,6 +581,48 @@ def set_mix_fusion(on: bool) -> None:
     MIX_FUSION = bool(on)
 
 
+# Backward merge (docs/ARCHITECTURE.md "Backward merge"): set_bwd_merge /
+# GLOM_NO_BWD_MERGE=1, read once per glom_forward like the two above. Off
+# restores every launch of the unmerged backward, the dense trajectory
+# gradient included.
+BWD_MERGE = True
+
+
+def set_bwd_merge(on: bool) -> None:
+    global BWD_MERGE
+    BWD_MERGE = bool(on)
+
+
+class _BwdCarry:
+    """The backward's mirror of _LoopCarry: what step t's backward leaves
+    for step t-1's. ``put`` keeps (dLevels_t, dmix_next, first level of
+    dmix_next that was written); ``take`` hands dmix_next out only if the
+    gradient autograd delivers IS dLevels_t (same storage, shape and
+    strides, so nothing was added to it and no hook replaced it) and the
+    taker's cone starts no lower than what was written. The pair is dropped
+    after one ``take`` either way; the caller then computes dmix from the
+    gradient it was given. No host synchronisation: pointer compares only.
+
+    posz: the forward returns the trajectory, so the unmerged path would
+    add an all-zero slice to every step's dLevels (-0 becomes +0)."""
+
+    def __init__(self, posz):
+        self.posz = bool(posz)
+        self._pair = None
+
+    def put(self, dlevels, dmix_next, written_from):
+        self._pair = (dlevels, dmix_next, written_from)
+
+    def take(self, dnew, lo):
+        pair, self._pair = self._pair, None
+        if pair is None:
+            return None
+        dl, dm, written_from = pair
+        same = (dnew.data_ptr() == dl.data_ptr() and dnew.dtype == dl.dtype
+                and dnew.shape == dl.shape and dnew.stride() == dl.stride())
+        return dm if same and lo >= written_from else None
+
+
 class _LoopCarry:
     """What one glom_forward call carries from iteration to iteration
     besides `levels`. None of it is differentiable.
@@ -501,6 +645,7 @@ class _LoopCarry:
         self.td_in = None
         self.rnorm = None
         self.emit = False
+        self.bwd = None     # _BwdCarry, set by glom_forward when merging
 
     def set_next(self, td_in, rnorm):
         # the mix returns empty tensors where it does not emit (d != 512)
@@ -655,6 +800,16 @@ def glom_forward(model, img, iters, levels=None, return_all=False,
     n_sync = grad_iters if overlap else iters
 
     carry = _LoopCarry(levels)
+    # backward merge: needs the promise, 16-byte level rows, a top-down net
+    # and the default 3-way backward fork
+    merge = (loss_level_min is not None and BWD_MERGE
+             and os.environ.get("GLOM_NO_BWD_MERGE", "0") != "1"
+             and os.environ.get("GLOM_NO_BWD_STREAMS", "0") != "1"
+             and os.environ.get("GLOM_BWD_FORK", "3") == "3"
+             and model.dim % 8 == 0 and model.levels >= 2
+             and 0 < grad_iters <= iters and torch.is_grad_enabled())
+    if merge:
+        carry.bwd = _BwdCarry(posz=return_all)
 
     steps = [levels]
     with trace_range(f"glom/iterate x{iters}"):
@@ -713,5 +868,10 @@ def glom_forward(model, img, iters, levels=None, return_all=False,
                     slab.record_stream(s_tail)
 
     if return_all:
+        if merge:
+            traj = ConeTrajectoryFn.apply(slab, steps[grad_iters],
+                                          grad_iters)
+            traj._glom_steps = steps
+            return traj
         return TrajectoryFn.apply(slab, *steps)
     return levels

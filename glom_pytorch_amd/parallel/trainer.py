@@ -21,6 +21,7 @@ from torch import nn
 
 from glom_pytorch_amd.parallel.ddp import BucketedDDP
 from glom_pytorch_amd.parallel.failure import Heartbeat
+from glom_pytorch_amd.ops.functional import trajectory_at
 
 
 class _DecoderLinear(nn.Linear):
@@ -284,7 +285,7 @@ class DenoisingTrainer:
         all_levels = self.model(noised, iters=iters, return_all=True,
                                 grad_iters=t, overlap_tail=overlap,
                                 loss_level_min=self._loss_level_min())
-        top = all_levels[t, :, :, -1]
+        top = trajectory_at(all_levels, t)[:, :, -1]
         recon = self.decoder(top)
         loss = F.mse_loss(recon.float(), img.float())
         loss.backward()
@@ -336,10 +337,11 @@ class DenoisingTrainer:
         all_levels = self.model(noised, iters=iters, return_all=True,
                                 grad_iters=t, overlap_tail=overlap,
                                 loss_level_min=self._loss_level_min(True))
-        recon = self.decoder(all_levels[t, :, :, -1])
+        at_t = trajectory_at(all_levels, t)
+        recon = self.decoder(at_t[:, :, -1])
         clean = torch.cat((img, img))
         loss = F.mse_loss(recon.float(), clean.float())
-        lvl = all_levels[t, :, :, self.contrast_level]
+        lvl = at_t[:, :, self.contrast_level]
         loss = loss + self.contrast_weight * column_contrastive_loss(
             lvl[:B], lvl[B:], temperature=self.contrast_temperature,
             negatives=self.contrast_negatives)
@@ -376,7 +378,7 @@ class DenoisingTrainer:
         traj = self.model(noised, iters=iters, return_all=True,
                           grad_iters=t, overlap_tail=True,
                           loss_level_min=self._loss_level_min())
-        recon = self.decoder(traj[t, :, :, -1])
+        recon = self.decoder(trajectory_at(traj, t)[:, :, -1])
         return F.mse_loss(recon.float(), half.float()) * scale
 
     def _micro_step(self, img: torch.Tensor, iters: int,
