@@ -225,7 +225,7 @@ void set_nce_fast(bool on) { g_nce_fast = on ? 1 : 0; }
 
 // Epilogue preconditions, checked here or by the callers named:
 //   EPI_NONE / bias / colscale  every kernel
-//   EPI_GELUGRAD, EPI_GELU_PAIR every kernel but nt_fast3; aux / out2 set
+//   EPI_GELUGRAD, EPI_GELU_PAIR every kernel; aux / out2 set
 //   EPI_SOFTMAX, EPI_SMBWD      nt_fast4 only, launched directly by the
 //                               consensus ops (N == 256, d % 64 == 0)
 //   EPI_GELU                    nt5p only (ask nt5p_takes_up_proj() first)
@@ -453,6 +453,47 @@ void zero_unwritten_dx(void* dLevels, int64_t BN, int64_t L, int64_t d,
 // grouped feed-forward (bottom-up: mode 0, top-down: mode 1)
 // reference glom_pytorch.py:23-36 (GroupedFeedForward) applied at :134/:136
 
+// Pointer table of a bottom-up operand: group 0 is `tokens` (B,N,d; row
+// stride d), group g >= 1 is level slice g-1 of `levels` (B,N,L,d; row
+// stride L*d). Groups [first, G) go to entries 0 .. G-first-1.
+template <class Ptr>
+void token_level_table(Ptr* tab, long* ld, void* tokens,
+                       const torch::Tensor& levels, int64_t first, int64_t G,
+                       int64_t L, int64_t d) {
+    for (int64_t g = first; g < G; g++) {
+        tab[g - first] = g == 0 ? tokens : u16_at(levels, (g - 1) * d);
+        ld[g - first] = g == 0 ? d : L * d;
+    }
+}
+
+// The top-down input td_in = levels[..., 1:, :] + pos, (B,N,L-1,d): `ready`
+// where the forward saved it or the previous iteration's level mix wrote
+// it, else materialized here once, so that the GEMMs stream it with plain
+// 16B loads / glds.
+torch::Tensor td_input(const torch::Tensor& levels,
+                       const c10::optional<torch::Tensor>& pos_opt,
+                       const c10::optional<torch::Tensor>& ready,
+                       hipStream_t s) {
+    const int64_t B = levels.size(0), N = levels.size(1),
+                  L = levels.size(2), d = levels.size(3);
+    if (ready.has_value() && ready->numel() > 0) {
+        const torch::Tensor& td_in = *ready;
+        CHECK_IN(td_in);
+        TORCH_CHECK(td_in.dim() == 4 && td_in.size(0) == B
+                    && td_in.size(1) == N && td_in.size(2) == L - 1
+                    && td_in.size(3) == d, "td_in must be (B,N,L-1,d)");
+        return td_in;
+    }
+    TORCH_CHECK(pos_opt.has_value(), "top-down needs pos");
+    const torch::Tensor& pos = *pos_opt;
+    CHECK_IN(pos);
+    auto td_in = torch::empty({B, N, L - 1, d}, levels.options());
+    launch_add_pos(levels.data_ptr(), pos.data_ptr(), td_in.data_ptr(),
+                   td_in.numel(), (int)N, (int)L, (int)d, s);
+    check_launch();
+    return td_in;
+}
+
 std::vector<torch::Tensor> grouped_ff_fwd(
         c10::optional<torch::Tensor> tokens_opt, torch::Tensor levels,
         c10::optional<torch::Tensor> pos_opt, torch::Tensor w1,
@@ -498,25 +539,9 @@ std::vector<torch::Tensor> grouped_ff_fwd(
 
     torch::Tensor td_in;
     if (mode == 1) {
-        // materialize td_in = levels[..., 1:, :] + pos once, so the GEMM
-        // streams it with plain 16B loads / glds
         TORCH_CHECK(pos_opt.has_value(), "top-down needs pos");
-        auto pos = pos_opt.value();
-        CHECK_IN(pos);
-        if (td_in_ready.has_value()) {
-            // the previous iteration's level mix already wrote it
-            td_in = td_in_ready.value();
-            CHECK_IN(td_in);
-            TORCH_CHECK(td_in.dim() == 4 && td_in.size(0) == B
-                        && td_in.size(1) == N && td_in.size(2) == G
-                        && td_in.size(3) == d, "td_in must be (B,N,L-1,d)");
-        } else {
-            td_in = torch::empty({B, N, G, d}, opts);
-            launch_add_pos(levels.data_ptr(), pos.data_ptr(),
-                           td_in.data_ptr(), td_in.numel(), (int)N, (int)L,
-                           (int)d, s);
-            check_launch();
-        }
+        CHECK_IN((*pos_opt));
+        td_in = td_input(levels, pos_opt, td_in_ready, s);
     }
 
     // up-projection: Hpre_g = x_g @ W1_g^T + b1_g ; Hact_g = gelu(Hpre_g)
@@ -528,15 +553,8 @@ std::vector<torch::Tensor> grouped_ff_fwd(
             CHECK_IN(tokens);
             TORCH_CHECK(tokens.numel() == M * d, "tokens must be (B,N,d)");
             p.A.flags = OP_TABLE;
-            if (g0 == 0) {
-                p.Atab[0] = tokens.data_ptr();
-                p.Atabld[0] = d;
-            }
-            for (int64_t g = 1; g < G; g++) {
-                p.Atab[g - g0] = (const char*)levels.data_ptr()
-                                 + (g - 1) * d * 2;
-                p.Atabld[g - g0] = L * d;
-            }
+            token_level_table(p.Atab, p.Atabld, tokens.data_ptr(), levels,
+                              g0, G, L, d);
         } else {
             p.A.base = td_in.data_ptr();
             p.A.sin = d; p.A.ld = G * d;
@@ -579,6 +597,200 @@ std::vector<torch::Tensor> grouped_ff_fwd(
     return {Y, Hpre, Hact, td_in};
 }
 
+// ------------------------------------------------------------------ //
+// FF backward. Each stage exists once, below; grouped_ff_bwd runs them all
+// on the current stream, and ff_bwd_dh / ff_bwd_dx / ff_bwd_dw run the same
+// stages from three calls so that the python layer can fork them over
+// streams. Every stage takes the first live group (level cone) from the
+// shape and the row stride of dY where it reads dY.
+
+// One grouped FF problem. B, N, L and mode are known only to callers that
+// hold `levels` or its sizes (mode stays -1 otherwise); the dX and dW1
+// stages, which address level slices, need them.
+struct FFShape {
+    int64_t B = 0, N = 0, L = 0, d = 0;
+    int64_t G = 0, m4 = 0, M = 0;   // groups, hidden width, rows B*N
+    int64_t mode = -1;
+    int64_t g_lo = 0, Ga = 0;       // live groups [g_lo, G): Ga of them,
+                                    // the first at g_lo * (group stride)
+};
+
+FFShape ff_shape(int64_t G, int64_t M, int64_t m4, int64_t d, int64_t g_lo,
+                 int64_t B = 0, int64_t N = 0, int64_t L = 0,
+                 int64_t mode = -1) {
+    TORCH_CHECK(g_lo >= 0 && g_lo <= G, "g_lo out of range");
+    TORCH_CHECK(mode < 0 || (G == (mode == 0 ? L : L - 1) && M == B * N),
+                "FF operands do not match (B, N, L)");
+    FFShape f;
+    f.B = B; f.N = N; f.L = L; f.d = d;
+    f.G = G; f.m4 = m4; f.M = M;
+    f.mode = mode;
+    f.g_lo = g_lo; f.Ga = G - g_lo;
+    return f;
+}
+
+// Row stride of dY in elements: dy_ld, or G*d where it is 0. The top-down
+// call of the merged backward passes dmix (B,N,L,d) itself with
+// dy_ld = L*d: its first L-1 level slices are what the compact dtd copy
+// held.
+int64_t ff_dy_ld(const FFShape& f, const torch::Tensor& dY, int64_t dy_ld) {
+    const int64_t ldY = dy_ld > 0 ? dy_ld : f.G * f.d;
+    TORCH_CHECK(ldY >= f.G * f.d && (dy_ld == 0 || ldY % 8 == 0),
+                "dy_ld must be a multiple of 8 and at least G * d");
+    TORCH_CHECK(f.M == 0 || dY.numel() >= (f.M - 1) * ldY + f.G * f.d,
+                "dY is smaller than (M, G*d) at row stride dy_ld");
+    return ldY;
+}
+
+// The dX outputs. The scattered dX GEMM writes every level slice of dLevels
+// except one (mode 0: the top slice, which only the top-down path feeds;
+// mode 1: slice 0) and those of the dead groups; just these are zeroed
+// instead of a full-tensor fill, and with no_fill not even these, for a
+// consumer that knows the written range (grad_merge).
+torch::Tensor ff_dlevels(const FFShape& f, bool no_fill,
+                         const torch::TensorOptions& opts, hipStream_t s) {
+    auto dLevels = torch::empty({f.B, f.N, f.L, f.d}, opts);
+    if (!no_fill)
+        zero_unwritten_dx(dLevels.data_ptr(), f.M, f.L, f.d, f.mode, f.g_lo,
+                          s);
+    return dLevels;
+}
+
+// dTokens (mode 0; zero when group 0 is dead), else an empty tensor
+torch::Tensor ff_dtokens(const FFShape& f, const torch::TensorOptions& opts,
+                         hipStream_t s) {
+    if (f.mode != 0) return torch::empty({0}, opts);
+    auto dTokens = torch::empty({f.B, f.N, f.d}, opts);
+    if (f.g_lo > 0) zero_fill(dTokens.data_ptr(), f.M * f.d * 2, s);
+    return dTokens;
+}
+
+// dHpre_g = (dY_g @ W2_g) * gelu'(Hpre_g) -- NT with W2^T. When the 128x256
+// kernels serve it, the bias grad dB1 = colsum(dHpre) fuses into the
+// epilogue (saves a full re-read of the 400MB dHpre): returns the
+// per-64-row f32 partials for ff_db1, or an undefined tensor.
+torch::Tensor ff_dh(const FFShape& f, const torch::Tensor& dY, int64_t ldY,
+                    const torch::Tensor& w2t, const torch::Tensor& Hpre,
+                    const torch::Tensor& dHpre, hipStream_t s) {
+    const int64_t M = f.M, m4 = f.m4, d = f.d, g_lo = f.g_lo;
+    auto opts = dHpre.options();
+    const bool fused = (M % 128 == 0) && (m4 % 256 == 0) && (m4 >= 1024)
+                       && (d % 64 == 0);
+    torch::Tensor db1f;
+    GemmParams p = base_params(M, m4, d, LAYOUT_NT, f.Ga, f.Ga, 1.0f);
+    p.A.base = u16_at(dY, g_lo * d); p.A.sin = d; p.A.ld = ldY;
+    p.B.base = u16_at(w2t, g_lo * m4 * d); p.B.sin = m4 * d; p.B.ld = d;
+    p.Cbase = u16_at(dHpre, g_lo * M * m4); p.Csin = M * m4; p.Cld = m4;
+    p.epilogue = EPI_GELUGRAD;
+    p.aux_base = u16_at(Hpre, g_lo * M * m4);
+    p.aux_sin = M * m4; p.aux_ld = m4;
+    if (fused) {
+        // fully written by the epilogue
+        db1f = torch::empty({f.Ga, M / 64, m4}, opts.dtype(at::kFloat));
+        p.colsum_out = db1f.data_ptr<float>();
+        p.colsum_sin = (M / 64) * m4;
+    }
+    run_gemm(p, s, opts, true, f.G);
+    return db1f;
+}
+
+// dB1 of the live groups: the fixed-order finish of ff_dh's partials, or
+// the native deterministic column sum of dHpre
+void ff_db1(const FFShape& f, const torch::Tensor& db1f,
+            const torch::Tensor& dHpre, const torch::Tensor& dB1,
+            hipStream_t s) {
+    const int64_t M = f.M, m4 = f.m4;
+    if (db1f.defined()) {
+        launch_colsum_fin(db1f.data_ptr<float>(), u16_at(dB1, f.g_lo * m4),
+                          (int)f.Ga, m4, (int)(M / 64), s);
+    } else {
+        auto ws = torch::empty({(long)f.Ga * colsum_rb(M) * m4},
+                               dHpre.options().dtype(at::kFloat));
+        launch_colsum(u16_at(dHpre, f.g_lo * M * m4), ws.data_ptr<float>(),
+                      u16_at(dB1, f.g_lo * m4), (int)f.Ga, M, m4, s);
+    }
+    check_launch();
+}
+
+// dX_g = dHpre_g @ W1_g -- NT with W1^T, scattered into dTokens and the
+// level slices of dLevels
+void ff_dx(const FFShape& f, const torch::Tensor& dHpre,
+           const torch::Tensor& w1t, const torch::Tensor& dTokens,
+           const torch::Tensor& dLevels, hipStream_t s) {
+    const int64_t M = f.M, m4 = f.m4, d = f.d, g_lo = f.g_lo;
+    GemmParams p = base_params(M, d, m4, LAYOUT_NT, f.Ga, f.Ga, 1.0f);
+    p.A.base = u16_at(dHpre, g_lo * M * m4); p.A.sin = M * m4; p.A.ld = m4;
+    p.B.base = u16_at(w1t, g_lo * d * m4); p.B.sin = d * m4; p.B.ld = m4;
+    if (f.mode == 0) {
+        p.Cflags = OP_TABLE;
+        token_level_table(p.Ctab, p.Ctabld, dTokens.data_ptr(), dLevels,
+                          g_lo, f.G, f.L, d);
+    } else {
+        p.Cbase = u16_at(dLevels, (g_lo + 1) * d);
+        p.Csin = d; p.Cld = f.L * d;
+    }
+    run_gemm(p, s, dHpre.options(), true, f.G);
+}
+
+// dW1_g[h, j] = sum_m dHpre_g[m, h] * x_g[m, j]; x is tokens / levels
+// (mode 0) or td_in (mode 1)
+void ff_dw1(const FFShape& f, const torch::Tensor& dHpre,
+            const c10::optional<torch::Tensor>& tokens_opt,
+            const torch::Tensor& levels, const torch::Tensor& td_in,
+            const torch::Tensor& dW1, hipStream_t s) {
+    const int64_t M = f.M, m4 = f.m4, d = f.d, g_lo = f.g_lo;
+    GemmParams p = base_params(m4, d, M, LAYOUT_TN, f.Ga, f.Ga, 1.0f);
+    p.A.base = u16_at(dHpre, g_lo * M * m4); p.A.sin = M * m4; p.A.ld = m4;
+    if (f.mode == 0) {
+        const torch::Tensor& tokens = tokens_opt.value();
+        CHECK_IN(tokens);
+        p.B.flags = OP_TABLE;
+        token_level_table(p.Btab, p.Btabld, tokens.data_ptr(), levels, g_lo,
+                          f.G, f.L, d);
+    } else {
+        p.B.base = u16_at(td_in, g_lo * d);
+        p.B.sin = d; p.B.ld = f.G * d;
+    }
+    p.Cbase = u16_at(dW1, g_lo * m4 * d); p.Csin = m4 * d; p.Cld = d;
+    run_gemm(p, s, levels.options(), true, f.G);
+}
+
+// dW2_g[o, h] = sum_m dY_g[m, o] * Hact_g[m, h]
+void ff_dw2(const FFShape& f, const torch::Tensor& dY, int64_t ldY,
+            const torch::Tensor& Hact, const torch::Tensor& dW2,
+            hipStream_t s) {
+    const int64_t M = f.M, m4 = f.m4, d = f.d, g_lo = f.g_lo;
+    GemmParams p = base_params(d, m4, M, LAYOUT_TN, f.Ga, f.Ga, 1.0f);
+    p.A.base = u16_at(dY, g_lo * d); p.A.sin = d; p.A.ld = ldY;
+    p.B.base = u16_at(Hact, g_lo * M * m4); p.B.sin = M * m4; p.B.ld = m4;
+    p.Cbase = u16_at(dW2, g_lo * d * m4); p.Csin = d * m4; p.Cld = m4;
+    run_gemm(p, s, Hact.options(), true, f.G);
+}
+
+// dB2 = colsum over the M token rows of dY viewed as (M, G*d) at row stride
+// ldY; the dead groups' columns of dY are zero and sum to zero. Skipped
+// where the result came in ready (db2_cone).
+void ff_db2(const FFShape& f, const torch::Tensor& dY, int64_t ldY,
+            const torch::Tensor& dB2, bool ready, hipStream_t s) {
+    const int64_t M = f.M, Gd = f.G * f.d;
+    if (ready) return;
+    if (f.Ga == 0) {
+        zero_fill(dB2.data_ptr(), Gd * 2, s);
+        return;
+    }
+    auto ws = torch::empty({(long)colsum_rb(M) * Gd},
+                           dY.options().dtype(at::kFloat));
+    if (ldY == Gd)
+        launch_colsum(dY.data_ptr(), ws.data_ptr<float>(), dB2.data_ptr(), 1,
+                      M, Gd, s);
+    else    // same chains over the row-strided matrix
+        launch_colsum_cone(dY.data_ptr(), ws.data_ptr<float>(),
+                           dB2.data_ptr(), nullptr, M, Gd, 0, ldY, 0, s);
+    check_launch();
+}
+
+// dB2_ready: the dB2 result, already computed (db2_cone). no_fill: see
+// ff_dlevels. Launch order: fills, dH, dX, dW1, dW2, dB1 finish, dB2 sum.
 std::vector<torch::Tensor> grouped_ff_bwd(
         torch::Tensor dY, c10::optional<torch::Tensor> tokens_opt,
         torch::Tensor levels, c10::optional<torch::Tensor> pos_opt,
@@ -590,66 +802,38 @@ std::vector<torch::Tensor> grouped_ff_bwd(
         int64_t g_lo = 0, int64_t dy_ld = 0,
         c10::optional<torch::Tensor> dB2_ready = c10::nullopt,
         bool no_fill = false) {
-    // dy_ld (0 = G*d): row stride of dY in elements. The top-down call of
-    // the merged backward passes dmix (B,N,L,d) itself with dy_ld = L*d:
-    // its first L-1 level slices are what the compact dtd copy held.
-    // dB2_ready: the dB2 result, already computed (db2_cone); no column sum
-    // of dY is run. no_fill: the level slices of dLevels that no live group
-    // writes are left unwritten, for a consumer that knows the written
-    // range (grad_merge) instead of reading the zeros back.
     CHECK_IN(dY); CHECK_IN(levels); CHECK_IN(w1); CHECK_IN(w2); CHECK_IN(Hpre);
     CHECK_IN(Hact);
     const int64_t B = levels.size(0), N = levels.size(1),
                   L = levels.size(2), d = levels.size(3);
     const int64_t G = (mode == 0) ? L : L - 1;
     const int64_t m4 = w1.size(0) / G;
-    const int64_t M = B * N;
-    TORCH_CHECK(g_lo >= 0 && g_lo <= G, "g_lo out of range");
-    const int64_t ldY = dy_ld > 0 ? dy_ld : G * d;
-    TORCH_CHECK(ldY >= G * d && (dy_ld == 0 || ldY % 8 == 0),
-                "dy_ld must be a multiple of 8 and at least G * d");
-    TORCH_CHECK(M == 0 || dY.numel() >= (M - 1) * ldY + G * d,
-                "dY is smaller than (M, G*d) at row stride dy_ld");
-    if (dB2_ready.has_value()) {
-        CHECK_IN((*dB2_ready));
-        TORCH_CHECK(dB2_ready->numel() == G * d, "dB2_ready must be (G*d,)");
-    }
-    // live groups [g_lo, G): Ga of them, the first at element offsets
-    // g_lo * (group stride) into every per-group operand
-    const int64_t Ga = G - g_lo;
+    const FFShape f = ff_shape(G, B * N, m4, d, g_lo, B, N, L, mode);
+    const int64_t ldY = ff_dy_ld(f, dY, dy_ld);
     auto opts = levels.options();
     hipStream_t s = cur_stream();
 
-    // the scattered dX GEMM writes every level slice except one (mode 0:
-    // the top slice, which only the top-down path feeds; mode 1: slice 0)
-    // and those of the dead groups; zero just these instead of a
-    // full-tensor fill
-    auto dLevels = torch::empty({B, N, L, d}, opts);
-    if (!no_fill)
-        zero_unwritten_dx(dLevels.data_ptr(), B * N, L, d, mode, g_lo, s);
-    torch::Tensor dTokens;
+    const bool ready = dB2_ready.has_value();
+    if (ready) {
+        CHECK_IN((*dB2_ready));
+        TORCH_CHECK(dB2_ready->numel() == G * d, "dB2_ready must be (G*d,)");
+    }
+    auto dLevels = ff_dlevels(f, no_fill, opts, s);
     auto dW1 = torch::empty({G * m4, d}, opts);
     auto dW2 = torch::empty({G * d, m4}, opts);
     auto dB1 = torch::empty({G * m4}, opts);
-    auto dB2 = dB2_ready.has_value() ? *dB2_ready
-                                     : torch::empty({G * d}, opts);
+    auto dB2 = ready ? *dB2_ready : torch::empty({G * d}, opts);
     zero_fill(dW1.data_ptr(), g_lo * m4 * d * 2, s);
     zero_fill(dW2.data_ptr(), g_lo * d * m4 * 2, s);
     zero_fill(dB1.data_ptr(), g_lo * m4 * 2, s);
-    if (mode == 0) {
-        dTokens = torch::empty({B, N, d}, opts);
-        if (g_lo > 0) zero_fill(dTokens.data_ptr(), M * d * 2, s);
-    } else {
-        dTokens = torch::empty({0}, opts);
-    }
-    if (Ga == 0) {
-        // nothing live: the fills are the whole result
-        if (!dB2_ready.has_value()) zero_fill(dB2.data_ptr(), G * d * 2, s);
+    auto dTokens = ff_dtokens(f, opts, s);
+    if (f.Ga == 0) {   // nothing live: the fills are the whole result
+        ff_db2(f, dY, ldY, dB2, ready, s);
         return {dTokens, dLevels, dW1, dB1, dW2, dB2};
     }
-    TORCH_CHECK(Hpre.numel() == G * M * m4 && Hact.numel() == G * M * m4,
+    TORCH_CHECK(Hpre.numel() == G * f.M * m4 && Hact.numel() == G * f.M * m4,
                 "Hpre / Hact must be (G, M, m4)");
-    auto dHpre = torch::empty({G, M, m4}, opts);
+    auto dHpre = torch::empty({G, f.M, m4}, opts);
 
     // per-group weight transposes turn the NN data grads into NT GEMMs
     // (callers that run many iterations pass them in, computed once)
@@ -659,121 +843,118 @@ std::vector<torch::Tensor> grouped_ff_bwd(
     auto w2t = w2t_opt.has_value()
         ? w2t_opt.value()
         : w2.view({G, d, m4}).transpose(1, 2).contiguous();   // (G,m4,d)
-
     torch::Tensor td_in;
-    if (mode == 1) {
-        if (td_in_opt.has_value() && td_in_opt->numel() > 0) {
-            td_in = td_in_opt.value();   // saved by the forward
-        } else {
-            auto pos = pos_opt.value();
-            CHECK_IN(pos);
-            td_in = torch::empty({B, N, G, d}, opts);
-            launch_add_pos(levels.data_ptr(), pos.data_ptr(),
-                           td_in.data_ptr(), td_in.numel(), (int)N, (int)L,
-                           (int)d, s);
-            check_launch();
-        }
-    }
+    if (mode == 1) td_in = td_input(levels, pos_opt, td_in_opt, s);
 
-    // dHpre = (dY_g @ W2_g) * gelu'(Hpre_g)  -- NT with W2^T; when the
-    // 128x256 kernel serves it, the bias grad dB1 = colsum(dHpre) fuses
-    // into its epilogue (saves a full re-read of the 400MB dHpre)
-    const bool dh_nt3 = (M % 128 == 0) && (m4 % 256 == 0) && (m4 >= 1024)
-                        && (d % 64 == 0);
-    torch::Tensor db1f;
-    {
-        GemmParams p = base_params(M, m4, d, LAYOUT_NT, Ga, Ga, 1.0f);
-        p.A.base = u16_at(dY, g_lo * d); p.A.sin = d; p.A.ld = ldY;
-        p.B.base = u16_at(w2t, g_lo * m4 * d); p.B.sin = m4 * d; p.B.ld = d;
-        p.Cbase = u16_at(dHpre, g_lo * M * m4); p.Csin = M * m4; p.Cld = m4;
-        p.epilogue = EPI_GELUGRAD;
-        p.aux_base = u16_at(Hpre, g_lo * M * m4);
-        p.aux_sin = M * m4; p.aux_ld = m4;
-        if (dh_nt3) {
-            // per-64-row partials, fully written by the epilogue
-            db1f = torch::empty({Ga, M / 64, m4}, opts.dtype(at::kFloat));
-            p.colsum_out = db1f.data_ptr<float>();
-            p.colsum_sin = (M / 64) * m4;
-        }
-        run_gemm(p, s, opts, true, G);
-    }
-    // dX_g = dHpre_g @ W1_g -- NT with W1^T, scattered into level slices
-    {
-        GemmParams p = base_params(M, d, m4, LAYOUT_NT, Ga, Ga, 1.0f);
-        p.A.base = u16_at(dHpre, g_lo * M * m4); p.A.sin = M * m4; p.A.ld = m4;
-        p.B.base = u16_at(w1t, g_lo * d * m4); p.B.sin = d * m4; p.B.ld = m4;
-        if (mode == 0) {
-            p.Cflags = OP_TABLE;
-            for (int64_t g = g_lo; g < G; g++) {
-                p.Ctab[g - g_lo] = g == 0 ? dTokens.data_ptr()
-                                          : u16_at(dLevels, (g - 1) * d);
-                p.Ctabld[g - g_lo] = g == 0 ? d : L * d;
-            }
-        } else {
-            p.Cbase = u16_at(dLevels, (g_lo + 1) * d);
-            p.Csin = d; p.Cld = L * d;
-        }
-        run_gemm(p, s, opts, true, G);
-    }
-    // dW1_g[h, j] = sum_m dHpre_g[m, h] * x_g[m, j]
-    {
-        GemmParams p = base_params(m4, d, M, LAYOUT_TN, Ga, Ga, 1.0f);
-        p.A.base = u16_at(dHpre, g_lo * M * m4); p.A.sin = M * m4; p.A.ld = m4;
-        if (mode == 0) {
-            auto tokens = tokens_opt.value();
-            CHECK_IN(tokens);
-            p.B.flags = OP_TABLE;
-            for (int64_t g = g_lo; g < G; g++) {
-                p.Btab[g - g_lo] = g == 0 ? tokens.data_ptr()
-                                          : u16_at(levels, (g - 1) * d);
-                p.Btabld[g - g_lo] = g == 0 ? d : L * d;
-            }
-        } else {
-            p.B.base = u16_at(td_in, g_lo * d);
-            p.B.sin = d; p.B.ld = G * d;
-        }
-        p.Cbase = u16_at(dW1, g_lo * m4 * d); p.Csin = m4 * d; p.Cld = d;
-        run_gemm(p, s, opts, true, G);
-    }
-    // dW2_g[o, h] = sum_m dY_g[m, o] * Hact_g[m, h]
-    {
-        GemmParams p = base_params(d, m4, M, LAYOUT_TN, Ga, Ga, 1.0f);
-        p.A.base = u16_at(dY, g_lo * d); p.A.sin = d; p.A.ld = ldY;
-        p.B.base = u16_at(Hact, g_lo * M * m4); p.B.sin = M * m4; p.B.ld = m4;
-        p.Cbase = u16_at(dW2, g_lo * d * m4); p.Csin = d * m4; p.Cld = m4;
-        run_gemm(p, s, opts, true, G);
-    }
-    if (dh_nt3) {
-        launch_colsum_fin(db1f.data_ptr<float>(), u16_at(dB1, g_lo * m4),
-                          (int)Ga, m4, (int)(M / 64), s);
-        check_launch();
-    } else {
-        // native deterministic column sum (replaces ATen .sum(1))
-        auto ws = torch::empty({(long)Ga * colsum_rb(M) * m4},
-                               opts.dtype(at::kFloat));
-        launch_colsum(u16_at(dHpre, g_lo * M * m4), ws.data_ptr<float>(),
-                      u16_at(dB1, g_lo * m4), (int)Ga, M, m4, s);
-        check_launch();
-    }
-    // dB2 = colsum over the M token rows of dY viewed as (M, G*d); the
-    // dead groups' columns of dY are zero and sum to zero
-    if (!dB2_ready.has_value()) {
-        auto ws = torch::empty({(long)colsum_rb(M) * G * d},
-                               opts.dtype(at::kFloat));
-        if (ldY == G * d)
-            launch_colsum(dY.data_ptr(), ws.data_ptr<float>(),
-                          dB2.data_ptr(), 1, M, G * d, s);
-        else    // same chains over the row-strided matrix
-            launch_colsum_cone(dY.data_ptr(), ws.data_ptr<float>(),
-                               dB2.data_ptr(), nullptr, M, G * d, 0, ldY, 0,
-                               s);
-        check_launch();
-    }
+    auto db1f = ff_dh(f, dY, ldY, w2t, Hpre, dHpre, s);
+    ff_dx(f, dHpre, w1t, dTokens, dLevels, s);
+    ff_dw1(f, dHpre, tokens_opt, levels, td_in, dW1, s);
+    ff_dw2(f, dY, ldY, Hact, dW2, s);
+    ff_db1(f, db1f, dHpre, dB1, s);
+    ff_db2(f, dY, ldY, dB2, ready, s);
     return {dTokens, dLevels, dW1, dB1, dW2, dB2};
 }
 
+// The three calls take the first live group `g_lo` like grouped_ff_bwd:
+// dHpre keeps its (G, M, m4) shape, its dead groups are neither written by
+// ff_bwd_dh nor read by the two calls after it. ff_bwd_dh finishes dB1
+// directly after its GEMM.
+std::vector<torch::Tensor> ff_bwd_dh(torch::Tensor dY, torch::Tensor w2t,
+                                     torch::Tensor Hpre, int64_t g_lo = 0) {
+    CHECK_IN(dY); CHECK_IN(w2t); CHECK_IN(Hpre);
+    TORCH_CHECK(Hpre.dim() == 3, "Hpre must be (G, M, m4)");
+    const FFShape f = ff_shape(Hpre.size(0), Hpre.size(1), Hpre.size(2),
+                               dY.size(3), g_lo);
+    const int64_t ldY = ff_dy_ld(f, dY, 0);
+    auto opts = dY.options();
+    hipStream_t s = cur_stream();
+    auto dHpre = torch::empty({f.G, f.M, f.m4}, opts);
+    auto dB1 = torch::empty({f.G * f.m4}, opts);
+    zero_fill(dB1.data_ptr(), g_lo * f.m4 * 2, s);
+    if (f.Ga == 0) return {dHpre, dB1};
+    auto db1f = ff_dh(f, dY, ldY, w2t, Hpre, dHpre, s);
+    ff_db1(f, db1f, dHpre, dB1, s);
+    return {dHpre, dB1};
+}
+
+std::vector<torch::Tensor> ff_bwd_dx(torch::Tensor dHpre, torch::Tensor w1t,
+                                     c10::optional<torch::Tensor> tokens_opt,
+                                     int64_t B, int64_t N, int64_t L,
+                                     int64_t mode, int64_t g_lo = 0) {
+    CHECK_IN(dHpre); CHECK_IN(w1t);
+    const int64_t G = dHpre.size(0), M = dHpre.size(1), m4 = dHpre.size(2);
+    const FFShape f = ff_shape(G, M, m4, w1t.numel() / (G * m4), g_lo, B, N,
+                               L, mode);
+    if (mode == 0) { CHECK_IN(tokens_opt.value()); }
+    hipStream_t s = cur_stream();
+    auto dLevels = ff_dlevels(f, false, dHpre.options(), s);
+    auto dTokens = ff_dtokens(f, dHpre.options(), s);
+    if (f.Ga > 0) ff_dx(f, dHpre, w1t, dTokens, dLevels, s);
+    return {dTokens, dLevels};
+}
+
+// Launch order: dW1, dW2, dB2.
+std::vector<torch::Tensor> ff_bwd_dw(
+        torch::Tensor dY, torch::Tensor dHpre,
+        c10::optional<torch::Tensor> tokens_opt, torch::Tensor levels,
+        c10::optional<torch::Tensor> pos_opt, torch::Tensor Hact,
+        int64_t mode,
+        c10::optional<torch::Tensor> td_in_opt = c10::nullopt,
+        int64_t g_lo = 0) {
+    CHECK_IN(dY); CHECK_IN(dHpre); CHECK_IN(levels); CHECK_IN(Hact);
+    const int64_t G = dHpre.size(0), M = dHpre.size(1), m4 = dHpre.size(2);
+    const int64_t d = levels.size(3);
+    const FFShape f = ff_shape(G, M, m4, d, g_lo, levels.size(0),
+                               levels.size(1), levels.size(2), mode);
+    const int64_t ldY = ff_dy_ld(f, dY, 0);
+    auto opts = levels.options();
+    hipStream_t s = cur_stream();
+    auto dW1 = torch::empty({G * m4, d}, opts);
+    auto dW2 = torch::empty({G * d, m4}, opts);
+    auto dB2 = torch::empty({G * d}, opts);
+    zero_fill(dW1.data_ptr(), g_lo * m4 * d * 2, s);
+    zero_fill(dW2.data_ptr(), g_lo * d * m4 * 2, s);
+    if (f.Ga > 0) {
+        torch::Tensor td_in;
+        if (mode == 1) td_in = td_input(levels, pos_opt, td_in_opt, s);
+        ff_dw1(f, dHpre, tokens_opt, levels, td_in, dW1, s);
+        ff_dw2(f, dY, ldY, Hact, dW2, s);
+    }
+    ff_db2(f, dY, ldY, dB2, false, s);
+    return {dW1, dW2, dB2};
+}
+
+
 // ------------------------------------------------------------------ //
 // consensus attention (reference glom_pytorch.py:38-73)
+
+// One GEMM operand per (batch, level): the three bf16 buffer shapes of the
+// consensus ops, entered at level l_lo (0 in the forward; nInner = L - l_lo)
+struct LevelOp {
+    void* base; long sin, sout, ld;
+    operator OpArg() const { return OpArg{base, sin, sout, ld, 0}; }
+};
+// (B,N,L,d): level slices, rows L*d apart
+LevelOp op_bnld(const torch::Tensor& t, int64_t l_lo = 0) {
+    const long N = t.size(1), L = t.size(2), d = t.size(3);
+    return {u16_at(t, l_lo * d), d, N * L * d, L * d};
+}
+// (B,L,N,N) and (B,L,N,d): one compact matrix per level
+LevelOp op_bl(const torch::Tensor& t, int64_t l_lo = 0) {
+    const long L = t.size(1), R = t.size(2), C = t.size(3);
+    return {u16_at(t, l_lo * R * C), R * C, L * R * C, C};
+}
+void set_c(GemmParams& p, const LevelOp& o) {
+    p.Cbase = o.base; p.Csin = o.sin; p.Csout = o.sout; p.Cld = o.ld;
+}
+void set_aux(GemmParams& p, const LevelOp& o) {
+    p.aux_base = o.base; p.aux_sin = o.sin; p.aux_sout = o.sout;
+    p.aux_ld = o.ld;
+}
+void set_out2(GemmParams& p, const LevelOp& o) {
+    p.out2 = o.base; p.out2_sin = o.sin; p.out2_sout = o.sout;
+    p.out2_ld = o.ld;
+}
 
 std::vector<torch::Tensor> consensus_fwd(
         torch::Tensor levels, bool attend_self,
@@ -819,25 +1000,22 @@ std::vector<torch::Tensor> consensus_fwd(
     {
         GemmParams p = base_params(N, N, d, LAYOUT_NT, P, L,
                                    (float)std::pow((double)d, -0.5));
-        p.A.base = levels.data_ptr(); p.A.sin = d; p.A.sout = N * L * d;
-        p.A.ld = L * d;
+        p.A = op_bnld(levels);
         p.B = p.A;
-        p.Cbase = probs.data_ptr(); p.Csin = N * N; p.Csout = L * N * N;
-        p.Cld = N;
+        set_c(p, op_bl(probs));
         p.colscale_base = rnorm.data_ptr<float>();
         p.cs_sin = N; p.cs_sout = L * N; p.has_colscale = 1;
         if (fused_sm) {
-            // the nt3 tile spans whole rows: softmax fuses into the epilogue
+            // nt_fast4's 256-wide tile spans whole rows: softmax fuses into
+            // the epilogue
             p.epilogue = EPI_SOFTMAX;
             p.self_mask = attend_self ? 0 : 1;
             p.nlmask = mask;
             p.splitk = 1;
             if (fuse_av) {
                 // AV product fused too: O computed from the LDS-resident P
-                p.out2 = out_av.data_ptr();
-                p.out2_sin = d; p.out2_sout = N * L * d; p.out2_ld = L * d;
-                p.aux_base = levels.data_ptr();
-                p.aux_sin = d; p.aux_sout = N * L * d; p.aux_ld = L * d;
+                set_out2(p, op_bnld(out_av));
+                set_aux(p, op_bnld(levels));
                 p.npatch = (int)d;
             }
             launch_gemm_nt_fast4(p, s);
@@ -855,12 +1033,9 @@ std::vector<torch::Tensor> consensus_fwd(
     auto out = torch::empty({B, N, L, d}, opts);
     {
         GemmParams p = base_params(N, d, N, LAYOUT_NN, P, L, 1.0f);
-        p.A.base = probs.data_ptr(); p.A.sin = N * N; p.A.sout = L * N * N;
-        p.A.ld = N;
-        p.B.base = levels.data_ptr(); p.B.sin = d; p.B.sout = N * L * d;
-        p.B.ld = L * d;
-        p.Cbase = out.data_ptr(); p.Csin = d; p.Csout = N * L * d;
-        p.Cld = L * d;
+        p.A = op_bl(probs);
+        p.B = op_bnld(levels);
+        set_c(p, op_bnld(out));
         run_gemm(p, s, opts, lds_ok);
     }
     return {out, probs, rnorm};
@@ -881,6 +1056,10 @@ torch::Tensor consensus_bwd(torch::Tensor dOut, torch::Tensor levels,
     const int64_t B = levels.size(0), N = levels.size(1),
                   L = levels.size(2), d = levels.size(3);
     TORCH_CHECK(l_lo >= 0 && l_lo <= L, "l_lo out of range");
+    TORCH_CHECK(dOut.sizes() == levels.sizes() && probs.dim() == 4
+                && probs.size(1) == L && probs.size(2) == N
+                && probs.size(3) == N,
+                "dOut must be (B,N,L,d) like levels, probs (B,L,N,N)");
     const int64_t Ll = L - l_lo;
     const int64_t P = B * Ll;       // live problems
     const int64_t Pfull = B * L;    // what the dispatch gates are judged by
@@ -899,89 +1078,67 @@ torch::Tensor consensus_bwd(torch::Tensor dOut, torch::Tensor levels,
     if (Ll == 0) return dLevels;
     TORCH_CHECK(l_lo == 0 || d % 8 == 0, "l_lo needs dim % 8 == 0");
     const float* rn = rnorm.data_ptr<float>();
-    // level l_lo of a (B,N,L,d) / (B,L,N,N) / (B,L,N,d) bf16 buffer
-    auto lv = [&](const torch::Tensor& t) { return u16_at(t, l_lo * d); };
-    auto nn = [&](const torch::Tensor& t) { return u16_at(t, l_lo * N * N); };
+    const float scale = (float)std::pow((double)d, -0.5);
 
     // dP[i,j] = dOut_i . v_j, then row softmax backward -> dS, dSr
     const bool fused_sm = (N == 256) && (d % 64 == 0) && lds_ok;
     auto dS = torch::empty({B, L, N, N}, opts);
     auto dSr = torch::empty({B, L, N, N}, opts);
     torch::Tensor dP;
-    if (fused_sm) {
+    {
         GemmParams p = base_params(N, N, d, LAYOUT_NT, P, Ll, 1.0f);
-        p.A.base = lv(dOut); p.A.sin = d; p.A.sout = N * L * d;
-        p.A.ld = L * d;
-        p.B.base = lv(levels); p.B.sin = d; p.B.sout = N * L * d;
-        p.B.ld = L * d;
-        p.Cbase = nn(dS); p.Csin = N * N; p.Csout = L * N * N;
-        p.Cld = N;
-        p.epilogue = EPI_SMBWD;
-        p.aux_base = nn(probs);
-        p.aux_sin = N * N; p.aux_sout = L * N * N; p.aux_ld = N;
-        p.out2 = nn(dSr);
-        p.out2_sin = N * N; p.out2_sout = L * N * N; p.out2_ld = N;
-        p.colscale_base = rn + l_lo * N;
-        p.cs_sin = N; p.cs_sout = L * N; p.has_colscale = 1;
-        p.self_mask = attend_self ? 0 : 1;
-        p.nlmask = mask;
-        p.alpha2 = (float)std::pow((double)d, -0.5);
-        p.splitk = 1;
-        launch_gemm_nt_fast4(p, s);
-        check_launch();
-    } else {
-        dP = torch::empty({B, L, N, N}, opts);
-        GemmParams p = base_params(N, N, d, LAYOUT_NT, P, Ll, 1.0f);
-        p.A.base = lv(dOut); p.A.sin = d; p.A.sout = N * L * d;
-        p.A.ld = L * d;
-        p.B.base = lv(levels); p.B.sin = d; p.B.sout = N * L * d;
-        p.B.ld = L * d;
-        p.Cbase = nn(dP); p.Csin = N * N; p.Csout = L * N * N;
-        p.Cld = N;
-        run_gemm(p, s, opts, lds_ok, Pfull);
-        launch_softmax_bwd(probs.data_ptr(), dP.data_ptr(), rn,
-                           dS.data_ptr(), dSr.data_ptr(), mask, (int)P,
-                           (int)N, attend_self ? 0 : 1,
-                           (float)std::pow((double)d, -0.5), s, (int)L,
-                           (int)l_lo);
-        check_launch();
+        p.A = op_bnld(dOut, l_lo);
+        p.B = op_bnld(levels, l_lo);
+        if (fused_sm) {
+            set_c(p, op_bl(dS, l_lo));
+            p.epilogue = EPI_SMBWD;
+            set_aux(p, op_bl(probs, l_lo));
+            set_out2(p, op_bl(dSr, l_lo));
+            p.colscale_base = rn + l_lo * N;
+            p.cs_sin = N; p.cs_sout = L * N; p.has_colscale = 1;
+            p.self_mask = attend_self ? 0 : 1;
+            p.nlmask = mask;
+            p.alpha2 = scale;
+            p.splitk = 1;
+            launch_gemm_nt_fast4(p, s);
+            check_launch();
+        } else {
+            dP = torch::empty({B, L, N, N}, opts);
+            set_c(p, op_bl(dP, l_lo));
+            run_gemm(p, s, opts, lds_ok, Pfull);
+            launch_softmax_bwd(probs.data_ptr(), dP.data_ptr(), rn,
+                               dS.data_ptr(), dSr.data_ptr(), mask, (int)P,
+                               (int)N, attend_self ? 0 : 1, scale, s, (int)L,
+                               (int)l_lo);
+            check_launch();
+        }
     }
 
     // dv[j,:] = sum_i P[i,j] dOut[i,:]
     auto dv = torch::empty({B, N, L, d}, opts);
     {
         GemmParams p = base_params(N, d, N, LAYOUT_TN, P, Ll, 1.0f);
-        p.A.base = nn(probs); p.A.sin = N * N; p.A.sout = L * N * N;
-        p.A.ld = N;
-        p.B.base = lv(dOut); p.B.sin = d; p.B.sout = N * L * d;
-        p.B.ld = L * d;
-        p.Cbase = lv(dv); p.Csin = d; p.Csout = N * L * d;
-        p.Cld = L * d;
+        p.A = op_bl(probs, l_lo);
+        p.B = op_bnld(dOut, l_lo);
+        set_c(p, op_bnld(dv, l_lo));
         run_gemm(p, s, opts, lds_ok, Pfull);
     }
     // dq[i,:] = sum_j dSr[i,j] levels[j,:]
     auto dq = torch::empty({B, N, L, d}, opts);
     {
         GemmParams p = base_params(N, d, N, LAYOUT_NN, P, Ll, 1.0f);
-        p.A.base = nn(dSr); p.A.sin = N * N; p.A.sout = L * N * N;
-        p.A.ld = N;
-        p.B.base = lv(levels); p.B.sin = d; p.B.sout = N * L * d;
-        p.B.ld = L * d;
-        p.Cbase = lv(dq); p.Csin = d; p.Csout = N * L * d;
-        p.Cld = L * d;
+        p.A = op_bl(dSr, l_lo);
+        p.B = op_bnld(levels, l_lo);
+        set_c(p, op_bnld(dq, l_lo));
         run_gemm(p, s, opts, lds_ok, Pfull);
     }
     // dkhat[j,:] = sum_i dS[i,j] levels[i,:]   (layout (B,L,N,d))
     auto dkhat = torch::empty({B, L, N, d}, opts);
     {
         GemmParams p = base_params(N, d, N, LAYOUT_TN, P, Ll, 1.0f);
-        p.A.base = nn(dS); p.A.sin = N * N; p.A.sout = L * N * N;
-        p.A.ld = N;
-        p.B.base = lv(levels); p.B.sin = d; p.B.sout = N * L * d;
-        p.B.ld = L * d;
-        p.Cbase = u16_at(dkhat, l_lo * N * d);
-        p.Csin = N * d; p.Csout = L * N * d;
-        p.Cld = d;
+        p.A = op_bl(dS, l_lo);
+        p.B = op_bnld(levels, l_lo);
+        set_c(p, op_bl(dkhat, l_lo));
         run_gemm(p, s, opts, lds_ok, Pfull);
     }
     launch_knorm_combine(dkhat.data_ptr(), levels.data_ptr(), rn,
@@ -1364,180 +1521,6 @@ std::vector<torch::Tensor> db2_cone(torch::Tensor dmix, int64_t lo) {
                        (L - 1) * d, L * d, lo * d, cur_stream());
     check_launch();
     return {bu, td};
-}
-
-// ------------------------------------------------------------------ //
-// Fine-grained FF backward stages (stream-forked by the python layer):
-// dH (with fused dB1), then dX and dW independently.
-
-// The three stages take the first live group `g_lo` like grouped_ff_bwd
-// (level cone): dHpre keeps its (G, M, m4) shape, its dead groups are
-// neither written here nor read by the two stages after it.
-std::vector<torch::Tensor> ff_bwd_dh(torch::Tensor dY, torch::Tensor w2t,
-                                     torch::Tensor Hpre, int64_t g_lo = 0) {
-    CHECK_IN(dY); CHECK_IN(w2t); CHECK_IN(Hpre);
-    TORCH_CHECK(Hpre.dim() == 3, "Hpre must be (G, M, m4)");
-    const int64_t G = Hpre.size(0), M = Hpre.size(1), m4 = Hpre.size(2);
-    const int64_t d = dY.size(3);
-    TORCH_CHECK(g_lo >= 0 && g_lo <= G, "g_lo out of range");
-    const int64_t Ga = G - g_lo;
-    auto opts = dY.options();
-    hipStream_t s = cur_stream();
-    auto dHpre = torch::empty({G, M, m4}, opts);
-    auto dB1 = torch::empty({G * m4}, opts);
-    zero_fill(dB1.data_ptr(), g_lo * m4 * 2, s);
-    if (Ga == 0) return {dHpre, dB1};
-    const bool fused = (M % 128 == 0) && (m4 % 256 == 0) && (m4 >= 1024)
-                       && (d % 64 == 0);
-    torch::Tensor db1f;
-    GemmParams p = base_params(M, m4, d, LAYOUT_NT, Ga, Ga, 1.0f);
-    p.A.base = u16_at(dY, g_lo * d); p.A.sin = d; p.A.ld = G * d;
-    p.B.base = u16_at(w2t, g_lo * m4 * d); p.B.sin = m4 * d; p.B.ld = d;
-    p.Cbase = u16_at(dHpre, g_lo * M * m4); p.Csin = M * m4; p.Cld = m4;
-    p.epilogue = EPI_GELUGRAD;
-    p.aux_base = u16_at(Hpre, g_lo * M * m4);
-    p.aux_sin = M * m4; p.aux_ld = m4;
-    if (fused) {
-        // per-64-row partials, fully written by the epilogue
-        db1f = torch::empty({Ga, M / 64, m4}, opts.dtype(at::kFloat));
-        p.colsum_out = db1f.data_ptr<float>();
-        p.colsum_sin = (M / 64) * m4;
-    }
-    run_gemm(p, s, opts, true, G);
-    if (fused) {
-        launch_colsum_fin(db1f.data_ptr<float>(), u16_at(dB1, g_lo * m4),
-                          (int)Ga, m4, (int)(M / 64), s);
-        check_launch();
-    } else {
-        auto cws = torch::empty({(long)Ga * colsum_rb(M) * m4},
-                                opts.dtype(at::kFloat));
-        launch_colsum(u16_at(dHpre, g_lo * M * m4), cws.data_ptr<float>(),
-                      u16_at(dB1, g_lo * m4), (int)Ga, M, m4, s);
-        check_launch();
-    }
-    return {dHpre, dB1};
-}
-
-std::vector<torch::Tensor> ff_bwd_dx(torch::Tensor dHpre, torch::Tensor w1t,
-                                     c10::optional<torch::Tensor> tokens_opt,
-                                     int64_t B, int64_t N, int64_t L,
-                                     int64_t mode, int64_t g_lo = 0) {
-    CHECK_IN(dHpre); CHECK_IN(w1t);
-    const int64_t G = dHpre.size(0), M = dHpre.size(1), m4 = dHpre.size(2);
-    const int64_t d = w1t.numel() / (G * m4);
-    TORCH_CHECK(g_lo >= 0 && g_lo <= G, "g_lo out of range");
-    TORCH_CHECK(G == (mode == 0 ? L : L - 1) && M == B * N,
-                "dHpre does not match (B, N, L)");
-    const int64_t Ga = G - g_lo;
-    auto opts = dHpre.options();
-    hipStream_t s = cur_stream();
-    torch::Tensor dTokens;
-    auto dLevels = torch::empty({B, N, L, d}, opts);
-    zero_unwritten_dx(dLevels.data_ptr(), B * N, L, d, mode, g_lo, s);
-    if (mode == 0) {
-        auto tokens = tokens_opt.value();
-        CHECK_IN(tokens);
-        dTokens = torch::empty({B, N, d}, opts);
-        if (g_lo > 0) zero_fill(dTokens.data_ptr(), M * d * 2, s);
-    } else {
-        dTokens = torch::empty({0}, opts);
-    }
-    if (Ga == 0) return {dTokens, dLevels};
-    GemmParams p = base_params(M, d, m4, LAYOUT_NT, Ga, Ga, 1.0f);
-    p.A.base = u16_at(dHpre, g_lo * M * m4); p.A.sin = M * m4; p.A.ld = m4;
-    p.B.base = u16_at(w1t, g_lo * d * m4); p.B.sin = d * m4; p.B.ld = m4;
-    if (mode == 0) {
-        p.Cflags = OP_TABLE;
-        for (int64_t g = g_lo; g < G; g++) {
-            p.Ctab[g - g_lo] = g == 0 ? dTokens.data_ptr()
-                                      : u16_at(dLevels, (g - 1) * d);
-            p.Ctabld[g - g_lo] = g == 0 ? d : L * d;
-        }
-    } else {
-        p.Cbase = u16_at(dLevels, (g_lo + 1) * d);
-        p.Csin = d; p.Cld = L * d;
-    }
-    run_gemm(p, s, opts, true, G);
-    return {dTokens, dLevels};
-}
-
-std::vector<torch::Tensor> ff_bwd_dw(
-        torch::Tensor dY, torch::Tensor dHpre,
-        c10::optional<torch::Tensor> tokens_opt, torch::Tensor levels,
-        c10::optional<torch::Tensor> pos_opt, torch::Tensor Hact,
-        int64_t mode,
-        c10::optional<torch::Tensor> td_in_opt = c10::nullopt,
-        int64_t g_lo = 0) {
-    CHECK_IN(dY); CHECK_IN(dHpre); CHECK_IN(levels); CHECK_IN(Hact);
-    const int64_t B = levels.size(0), N = levels.size(1),
-                  L = levels.size(2), d = levels.size(3);
-    const int64_t G = dHpre.size(0), M = dHpre.size(1), m4 = dHpre.size(2);
-    TORCH_CHECK(g_lo >= 0 && g_lo <= G, "g_lo out of range");
-    TORCH_CHECK(G == (mode == 0 ? L : L - 1) && M == B * N,
-                "dHpre does not match levels");
-    const int64_t Ga = G - g_lo;
-    auto opts = levels.options();
-    hipStream_t s = cur_stream();
-    auto dW1 = torch::empty({G * m4, d}, opts);
-    auto dW2 = torch::empty({G * d, m4}, opts);
-    auto dB2 = torch::empty({G * d}, opts);
-    zero_fill(dW1.data_ptr(), g_lo * m4 * d * 2, s);
-    zero_fill(dW2.data_ptr(), g_lo * d * m4 * 2, s);
-    if (Ga == 0) {
-        zero_fill(dB2.data_ptr(), G * d * 2, s);
-        return {dW1, dW2, dB2};
-    }
-    torch::Tensor td_in;
-    if (mode == 1) {
-        if (td_in_opt.has_value() && td_in_opt->numel() > 0) {
-            td_in = td_in_opt.value();   // saved by the forward
-        } else {
-            auto pos = pos_opt.value();
-            CHECK_IN(pos);
-            td_in = torch::empty({B, N, G, d}, opts);
-            launch_add_pos(levels.data_ptr(), pos.data_ptr(),
-                           td_in.data_ptr(), td_in.numel(), (int)N, (int)L,
-                           (int)d, s);
-            check_launch();
-        }
-    }
-    {
-        GemmParams p = base_params(m4, d, M, LAYOUT_TN, Ga, Ga, 1.0f);
-        p.A.base = u16_at(dHpre, g_lo * M * m4);
-        p.A.sin = M * m4; p.A.ld = m4;
-        if (mode == 0) {
-            auto tokens = tokens_opt.value();
-            CHECK_IN(tokens);
-            p.B.flags = OP_TABLE;
-            for (int64_t g = g_lo; g < G; g++) {
-                p.Btab[g - g_lo] = g == 0 ? tokens.data_ptr()
-                                          : u16_at(levels, (g - 1) * d);
-                p.Btabld[g - g_lo] = g == 0 ? d : L * d;
-            }
-        } else {
-            p.B.base = u16_at(td_in, g_lo * d);
-            p.B.sin = d; p.B.ld = G * d;
-        }
-        p.Cbase = u16_at(dW1, g_lo * m4 * d); p.Csin = m4 * d; p.Cld = d;
-        run_gemm(p, s, opts, true, G);
-    }
-    {
-        GemmParams p = base_params(d, m4, M, LAYOUT_TN, Ga, Ga, 1.0f);
-        p.A.base = u16_at(dY, g_lo * d); p.A.sin = d; p.A.ld = G * d;
-        p.B.base = u16_at(Hact, g_lo * M * m4);
-        p.B.sin = M * m4; p.B.ld = m4;
-        p.Cbase = u16_at(dW2, g_lo * d * m4); p.Csin = d * m4; p.Cld = m4;
-        run_gemm(p, s, opts, true, G);
-    }
-    // the dead groups' columns of dY are zero and sum to zero
-    {
-        auto cws = torch::empty({(long)colsum_rb(M) * G * d},
-                                opts.dtype(at::kFloat));
-        launch_colsum(dY.data_ptr(), cws.data_ptr<float>(), dB2.data_ptr(),
-                      1, M, G * d, s);
-        check_launch();
-    }
-    return {dW1, dW2, dB2};
 }
 
 // ------------------------------------------------------------------ //

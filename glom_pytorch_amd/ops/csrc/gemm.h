@@ -9,7 +9,7 @@ enum GemmEpilogue {
     EPI_NONE = 0,
     EPI_GELUGRAD = 1,
     EPI_GELU_PAIR = 2,
-    // full-row fusions (tile spans the whole row, nt_fast3 only):
+    // full-row fusions (tile spans the whole row, nt_fast4 only):
     EPI_SOFTMAX = 3,   // consensus scores -> masked row softmax -> P
     EPI_SMBWD = 4,     // dP -> row softmax backward -> dS (C), dSr (out2)
     // C = gelu(bf16(acc*alpha + bias)): EPI_GELU_PAIR's out2 without the
@@ -143,7 +143,6 @@ void launch_gemm_tn_fast(const GemmParams& p, hipStream_t stream);
 void launch_gemm_nn_fast(const GemmParams& p, hipStream_t stream);
 // split-K NN (gemm_nn_sk.hip): f32 partials into p.ws[slice][problem][M][N]
 void launch_gemm_nn_sk(const GemmParams& p, hipStream_t stream);
-void launch_gemm_nt_fast3(const GemmParams& p, hipStream_t stream);
 void launch_gemm_nt_fast4(const GemmParams& p, hipStream_t stream);
 void launch_gemm_nt_fast5p(const GemmParams& p, hipStream_t stream);
 void launch_gemm_nt_fast8p(const GemmParams& p, hipStream_t stream);

@@ -9,6 +9,7 @@ reference's denoising recipe, README.md:56-90).
 
 from __future__ import annotations
 
+import collections
 import os
 
 import torch
@@ -264,61 +265,46 @@ class GlomStepFn(torch.autograd.Function):
         lo = cone[0] if cone is not None else 0
         save_td = save_for_bwd and (lo < levels.size(2) - 1
                                     or FORCE_SAVE_FOR_BWD)
-        if (torch.is_grad_enabled()
-                and os.environ.get("GLOM_FWD_STREAMS", "0") != "1"):
-            # never taken: grad mode is always disabled inside a custom
-            # Function.forward, so GLOM_FWD_STREAMS has no effect and
-            # training and inference both run the fork below
-            (out, bhp, bha, thp, tha, probs, rnorm,
-             tdin) = ext.glom_step_fwd(
-                tokens, levels, pos, bw1, bb1, bw2, bb2, tw1, tb1, tw2,
-                tb2, attend_self, mask, slab, sidx, save_for_bwd)
+        # the three per-iteration chains (bottom-up MLP, top-down MLP,
+        # consensus attention) only depend on `levels`; forking them onto
+        # side streams overlaps their tail waves (+10% forward throughput
+        # measured on inference).
+        cur = torch.cuda.current_stream()
+        s_td, s_at, _ = GlomStepFn._side_streams()
+        ev = torch.cuda.Event()
+        ev.record(cur)
+        buY, bhp, bha, _ = ext.grouped_ff_fwd(tokens, levels, None, bw1, bb1,
+                                              bw2, bb2, 0, save_for_bwd,
+                                              bu0 is not None)
+        with torch.cuda.stream(s_td):
+            s_td.wait_event(ev)
+            tdY, thp, tha, tdin = ext.grouped_ff_fwd(None, levels, pos, tw1,
+                                                     tb1, tw2, tb2, 1,
+                                                     save_td, False,
+                                                     td_ready)
+        with torch.cuda.stream(s_at):
+            s_at.wait_event(ev)
+            cons, probs, rnorm = ext.consensus_fwd(levels, attend_self,
+                                                   mask, rn_ready)
+        cur.wait_stream(s_td)
+        cur.wait_stream(s_at)
+        # boundary tensors crossing back to the main stream: pin their
+        # blocks until the main stream catches up (allocator safety)
+        for t in (tdY, thp, tha, tdin, cons, probs, rnorm):
+            if t.numel():
+                t.record_stream(cur)
+        if emit:
+            out, td_next, rn_next = ext.level_mix_fwd_next(
+                levels, buY, tdY, cons, slab, sidx, bu0, pos)
+            carry.set_next(td_next, rn_next)
+        else:
+            out = ext.level_mix_fwd(levels, buY, tdY, cons, slab, sidx, bu0)
             if carry is not None:
                 carry.set_next(None, None)
-        else:
-            # the three per-iteration chains (bottom-up MLP, top-down MLP,
-            # consensus attention) only depend on `levels`; forking them
-            # onto side streams overlaps their tail waves (+10% forward
-            # throughput measured on inference).
-            cur = torch.cuda.current_stream()
-            s_td, s_at, _ = GlomStepFn._side_streams()
-            ev = torch.cuda.Event()
-            ev.record(cur)
-            buY, bhp, bha, _ = ext.grouped_ff_fwd(tokens, levels, None,
-                                                  bw1, bb1, bw2, bb2, 0,
-                                                  save_for_bwd,
-                                                  bu0 is not None)
-            with torch.cuda.stream(s_td):
-                s_td.wait_event(ev)
-                tdY, thp, tha, tdin = ext.grouped_ff_fwd(None, levels, pos,
-                                                         tw1, tb1, tw2,
-                                                         tb2, 1,
-                                                         save_td, False,
-                                                         td_ready)
-            with torch.cuda.stream(s_at):
-                s_at.wait_event(ev)
-                cons, probs, rnorm = ext.consensus_fwd(levels, attend_self,
-                                                       mask, rn_ready)
-            cur.wait_stream(s_td)
-            cur.wait_stream(s_at)
-            # boundary tensors crossing back to the main stream: pin their
-            # blocks until the main stream catches up (allocator safety)
-            for t in (tdY, thp, tha, tdin, cons, probs, rnorm):
-                if t.numel():
-                    t.record_stream(cur)
-            if emit:
-                out, td_next, rn_next = ext.level_mix_fwd_next(
-                    levels, buY, tdY, cons, slab, sidx, bu0, pos)
-                carry.set_next(td_next, rn_next)
-            else:
-                out = ext.level_mix_fwd(levels, buY, tdY, cons, slab, sidx,
-                                        bu0)
-                if carry is not None:
-                    carry.set_next(None, None)
-            if carry is not None and carry.hoist and carry.bu0 is None:
-                # this step ran every group: keep its token-MLP output (a
-                # view into Y, row stride L*d) for the rest of the forward
-                carry.bu0 = buY[:, :, 0, :]
+        if carry is not None and carry.hoist and carry.bu0 is None:
+            # this step ran every group: keep its token-MLP output (a view
+            # into Y, row stride L*d) for the rest of the forward
+            carry.bu0 = buY[:, :, 0, :]
         ctx.save_for_backward(tokens, levels, pos, bw1, bw2, tw1, tw2,
                               bhp, bha, thp, tha, probs, rnorm, mask,
                               bw1t, bw2t, tw1t, tw2t, tdin)
@@ -336,14 +322,9 @@ class GlomStepFn(torch.autograd.Function):
         untouched; the top-down chain reads dmix with row stride L*d; dB2 is
         summed once; no chain zero-fills what it does not write, because
         grad_merge knows each contribution's range."""
-        ext = _load_extension()
-        (tokens, levels, pos, bw1, bw2, tw1, tw2, bhp, bha, thp, tha,
-         probs, rnorm, mask, bw1t, bw2t, tw1t, tw2t,
-         tdin) = ctx.saved_tensors
+        ext, sv, lo = _bwd_begin(ctx, dnew)
+        levels, t = sv.levels, ctx.cone[1]
         L, d = levels.size(2), levels.size(3)
-        lo, t = ctx.cone
-        if lo > 0 and CHECK_LEVEL_CONE:
-            _check_cone(dnew, lo, t)
         td_live = lo < L - 1
         cur = torch.cuda.current_stream()
         s_td, s_at, _ = GlomStepFn._side_streams()
@@ -356,28 +337,24 @@ class GlomStepFn(torch.autograd.Function):
         # the one dB2 column sum that both FF nets share
         with torch.cuda.stream(s_at):
             s_at.wait_event(ev)
-            dAttn = ext.consensus_bwd(dmix, levels, probs, rnorm,
-                                      ctx.attend_self, mask, lo, True)
+            dAttn = ext.consensus_bwd(dmix, levels, sv.probs, sv.rnorm,
+                                      ctx.attend_self, sv.mask, lo, True)
             db2_bu, db2_td = ext.db2_cone(dmix, lo)
         dmix.record_stream(s_at)
-        bu = ext.grouped_ff_bwd(dmix, tokens, levels, None, bw1, bw2,
-                                bhp, bha, 0, bw1t, bw2t, None, lo, 0,
-                                db2_bu, True)
-        if td_live:
-            with torch.cuda.stream(s_td):
+        bu = ext.grouped_ff_bwd(dmix, sv.tokens, levels, None, sv.bw1,
+                                sv.bw2, sv.bhp, sv.bha, 0, sv.bw1t, sv.bw2t,
+                                None, lo, 0, db2_bu, True)
+        # no live top-down group (lo + 1 == L): zero fills, no side stream
+        with torch.cuda.stream(s_td if td_live else None):
+            if td_live:
                 s_td.wait_event(ev)
-                td = ext.grouped_ff_bwd(dmix, None, levels, pos, tw1, tw2,
-                                        thp, tha, 1, tw1t, tw2t, tdin, lo,
-                                        L * d, db2_td, True)
-                dPos = ext.dpos(td[1], lo + 1)
+            td = ext.grouped_ff_bwd(dmix, None, levels, sv.pos, sv.tw1,
+                                    sv.tw2, sv.thp, sv.tha, 1, sv.tw1t,
+                                    sv.tw2t, sv.tdin, lo, L * d, db2_td, True)
+            dPos = ext.dpos(td[1], lo + 1)
+        if td_live:
             dmix.record_stream(s_td)
             cur.wait_stream(s_td)
-        else:
-            # no live top-down group: zero fills of the weight gradients
-            td = ext.grouped_ff_bwd(dmix, None, levels, pos, tw1, tw2,
-                                    thp, tha, 1, tw1t, tw2t, tdin, lo,
-                                    L * d, db2_td, True)
-            dPos = ext.dpos(td[1], L)
         cur.wait_stream(s_at)
         back = [dAttn, db2_bu, db2_td]
         if td_live:
@@ -390,117 +367,113 @@ class GlomStepFn(torch.autograd.Function):
                                             ctx.bwd.posz, want_next)
         if want_next:
             ctx.bwd.put(dLevels, dmix_next, max(lo - 1, 0))
-        return (bu[0], dLevels, dPos, bu[2], bu[3], bu[4], bu[5],
-                td[2], td[3], td[4], td[5], None, None, None, None,
-                None, None, None, None, None, None)
+        return _step_grads(bu[0], dLevels, dPos, bu[2], bu[3], bu[4], bu[5],
+                           td[2], td[3], td[4], td[5])
 
     @staticmethod
     def backward(ctx, dnew):
-        if (ctx.bwd is not None
-                and os.environ.get("GLOM_NO_BWD_STREAMS", "0") != "1"
-                and os.environ.get("GLOM_BWD_FORK", "3") == "3"):
-            return GlomStepFn._backward_merged(ctx, dnew)
-        ext = _load_extension()
-        (tokens, levels, pos, bw1, bw2, tw1, tw2, bhp, bha, thp, tha,
-         probs, rnorm, mask, bw1t, bw2t, tw1t, tw2t,
-         tdin) = ctx.saved_tensors
-        # level cone: groups / levels below lo carry an exactly-zero
-        # gradient; the ops skip them and fill in the zeros. The top-down
-        # MLP has groups 0..L-2: with lo = L-1 none is live (td_live)
-        L = levels.size(2)
-        lo = ctx.cone[0] if ctx.cone is not None else 0
-        if lo > 0 and CHECK_LEVEL_CONE:
-            _check_cone(dnew, lo, ctx.cone[1])
-        td_lo = min(lo, L - 1)
-        td_live = td_lo < L - 1
-        if os.environ.get("GLOM_NO_BWD_STREAMS", "0") == "1":
-            (dTokens, dLevels, dPos, dbw1, dbb1, dbw2, dbb2,
-             dtw1, dtb1, dtw2, dtb2) = ext.glom_step_bwd(
-                dnew.contiguous(), tokens, levels, pos, bw1, bw2, tw1, tw2,
-                bhp, bha, thp, tha, probs, rnorm, ctx.attend_self, mask,
-                bw1t, bw2t, tw1t, tw2t, tdin, lo)
-            return (dTokens, dLevels, dPos, dbw1, dbb1, dbw2, dbb2,
-                    dtw1, dtb1, dtw2, dtb2, None, None, None, None, None,
-                    None, None, None, None, None)
-        if os.environ.get("GLOM_BWD_FORK", "3") == "3":
-            cur = torch.cuda.current_stream()
-            s_td, s_at, _ = GlomStepFn._side_streams()
-            dmix, dtd = ext.level_mix_bwd(dnew.contiguous())
-            ev = torch.cuda.Event()
-            ev.record(cur)
-            bu = ext.grouped_ff_bwd(dmix, tokens, levels, None, bw1, bw2,
-                                    bhp, bha, 0, bw1t, bw2t, None, lo)
+        # the environment is read again here, a prepared carry is not enough
+        path = _bwd_path(merge=ctx.bwd is not None)
+        return getattr(GlomStepFn, "_backward_" + path)(ctx, dnew)
+
+    @staticmethod
+    def _backward_single(ctx, dnew):
+        """One extension call on the current stream."""
+        ext, sv, lo = _bwd_begin(ctx, dnew)
+        # the saved tensors in their order, attend_self before the mask
+        return _step_grads(*ext.glom_step_bwd(
+            dnew.contiguous(), *sv[:13], ctx.attend_self, *sv[13:], lo))
+
+    @staticmethod
+    def _backward_fork3(ctx, dnew):
+        """Bottom-up chain on the current stream, top-down and attention
+        chains on side streams. Groups / levels below lo carry an exactly-
+        zero gradient; the ops skip them and fill in the zeros. The top-down
+        MLP has groups 0..L-2: with lo = L-1 none is live (td_live)."""
+        ext, sv, lo = _bwd_begin(ctx, dnew)
+        levels, L = sv.levels, sv.levels.size(2)
+        td_lo, td_live = min(lo, L - 1), lo < L - 1
+        cur = torch.cuda.current_stream()
+        s_td, s_at, _ = GlomStepFn._side_streams()
+        dmix, dtd = ext.level_mix_bwd(dnew.contiguous())
+        ev = torch.cuda.Event()
+        ev.record(cur)
+        bu = ext.grouped_ff_bwd(dmix, sv.tokens, levels, None, sv.bw1,
+                                sv.bw2, sv.bhp, sv.bha, 0, sv.bw1t, sv.bw2t,
+                                None, lo)
+        # no live top-down group: only zero fills, no side stream
+        with torch.cuda.stream(s_td if td_live else None):
             if td_live:
-                with torch.cuda.stream(s_td):
-                    s_td.wait_event(ev)
-                    td = ext.grouped_ff_bwd(dtd, None, levels, pos, tw1,
-                                            tw2, thp, tha, 1, tw1t, tw2t,
-                                            tdin, td_lo)
-                dtd.record_stream(s_td)
-            else:
-                # no live top-down group: only zero fills, no side stream
-                td = ext.grouped_ff_bwd(dtd, None, levels, pos, tw1, tw2,
-                                        thp, tha, 1, tw1t, tw2t, tdin,
-                                        td_lo)
-            with torch.cuda.stream(s_at):
-                s_at.wait_event(ev)
-                dAttn = ext.consensus_bwd(dmix, levels, probs, rnorm,
-                                          ctx.attend_self, mask, lo)
-            dmix.record_stream(s_at)
-            if td_live:
-                cur.wait_stream(s_td)
-            cur.wait_stream(s_at)
-            for t in (list(td) if td_live else []) + [dAttn]:
-                if t is not None and t.numel():
-                    t.record_stream(cur)
-            dLevels = torch.empty_like(levels)
-            ext.add4_into(dmix, bu[1], td[1], dAttn, dLevels)
-            dPos = ext.dpos(td[1])
-            return (bu[0], dLevels, dPos, bu[2], bu[3], bu[4], bu[5],
-                    td[2], td[3], td[4], td[5], None, None, None, None,
-                    None, None, None, None, None, None)
-        # 4-way fork variant (weight grads on a dedicated stream): measured
-        # slightly SLOWER than the 3-way fork above (sync overhead), kept
-        # behind GLOM_BWD_FORK=4 for future tuning.
-        B, N = levels.size(0), levels.size(1)
+                s_td.wait_event(ev)
+            td = ext.grouped_ff_bwd(dtd, None, levels, sv.pos, sv.tw1,
+                                    sv.tw2, sv.thp, sv.tha, 1, sv.tw1t,
+                                    sv.tw2t, sv.tdin, td_lo)
+        if td_live:
+            dtd.record_stream(s_td)
+        with torch.cuda.stream(s_at):
+            s_at.wait_event(ev)
+            dAttn = ext.consensus_bwd(dmix, levels, sv.probs, sv.rnorm,
+                                      ctx.attend_self, sv.mask, lo)
+        dmix.record_stream(s_at)
+        if td_live:
+            cur.wait_stream(s_td)
+        cur.wait_stream(s_at)
+        for t in (list(td) if td_live else []) + [dAttn]:
+            if t is not None and t.numel():
+                t.record_stream(cur)
+        dLevels = torch.empty_like(levels)
+        ext.add4_into(dmix, bu[1], td[1], dAttn, dLevels)
+        dPos = ext.dpos(td[1])
+        return _step_grads(bu[0], dLevels, dPos, bu[2], bu[3], bu[4], bu[5],
+                           td[2], td[3], td[4], td[5])
+
+    @staticmethod
+    def _backward_fork4(ctx, dnew):
+        """fork3 with the weight gradients on a fourth stream: measured
+        slightly SLOWER (sync overhead), kept for future tuning."""
+        ext, sv, lo = _bwd_begin(ctx, dnew)
+        levels, pos = sv.levels, sv.pos
+        B, N, L = levels.size(0), levels.size(1), levels.size(2)
+        td_lo, td_live = min(lo, L - 1), lo < L - 1
         cur = torch.cuda.current_stream()
         s_td, s_at, s_w = GlomStepFn._side_streams()
         dmix, dtd = ext.level_mix_bwd(dnew.contiguous())
         ev0 = torch.cuda.Event()
         ev0.record(cur)
-        bu_dh, bu_db1 = ext.ff_bwd_dh(dmix, bw2t, bhp, lo)
+        bu_dh, bu_db1 = ext.ff_bwd_dh(dmix, sv.bw2t, sv.bhp, lo)
         ev_bu = torch.cuda.Event()
         ev_bu.record(cur)
         if td_live:
             with torch.cuda.stream(s_td):
                 s_td.wait_event(ev0)
-                td_dh, td_db1 = ext.ff_bwd_dh(dtd, tw2t, thp, td_lo)
+                td_dh, td_db1 = ext.ff_bwd_dh(dtd, sv.tw2t, sv.thp, td_lo)
                 ev_td = torch.cuda.Event()
                 ev_td.record(s_td)
         else:
             # no live top-down group: the op only zero-fills its six
             # results; neither s_td nor the top-down half of s_w is used
             (_, td_dl, td_w1, td_db1, td_w2, td_b2) = ext.grouped_ff_bwd(
-                dtd, None, levels, pos, tw1, tw2, thp, tha, 1, tw1t, tw2t,
-                tdin, td_lo)
+                dtd, None, levels, pos, sv.tw1, sv.tw2, sv.thp, sv.tha, 1,
+                sv.tw1t, sv.tw2t, sv.tdin, td_lo)
         with torch.cuda.stream(s_at):
             s_at.wait_event(ev0)
-            dAttn = ext.consensus_bwd(dmix, levels, probs, rnorm,
-                                      ctx.attend_self, mask, lo)
+            dAttn = ext.consensus_bwd(dmix, levels, sv.probs, sv.rnorm,
+                                      ctx.attend_self, sv.mask, lo)
         with torch.cuda.stream(s_w):
             s_w.wait_event(ev_bu)
-            bu_w1, bu_w2, bu_b2 = ext.ff_bwd_dw(dmix, bu_dh, tokens,
-                                                levels, None, bha, 0, None,
-                                                lo)
+            bu_w1, bu_w2, bu_b2 = ext.ff_bwd_dw(dmix, bu_dh, sv.tokens,
+                                                levels, None, sv.bha, 0,
+                                                None, lo)
             if td_live:
                 s_w.wait_event(ev_td)
                 td_w1, td_w2, td_b2 = ext.ff_bwd_dw(dtd, td_dh, None,
-                                                    levels, pos, tha, 1,
-                                                    tdin, td_lo)
-        bu_dt, bu_dl = ext.ff_bwd_dx(bu_dh, bw1t, tokens, B, N, L, 0, lo)
+                                                    levels, pos, sv.tha, 1,
+                                                    sv.tdin, td_lo)
+        bu_dt, bu_dl = ext.ff_bwd_dx(bu_dh, sv.bw1t, sv.tokens, B, N, L, 0,
+                                     lo)
         if td_live:
             with torch.cuda.stream(s_td):
-                _, td_dl = ext.ff_bwd_dx(td_dh, tw1t, None, B, N, L, 1,
+                _, td_dl = ext.ff_bwd_dx(td_dh, sv.tw1t, None, B, N, L, 1,
                                          td_lo)
         # cross-stream block pinning
         pins = [(dmix, s_at), (dmix, s_w), (bu_dh, s_w)]
@@ -520,9 +493,37 @@ class GlomStepFn(torch.autograd.Function):
         dLevels = torch.empty_like(levels)
         ext.add4_into(dmix, bu_dl, td_dl, dAttn, dLevels)
         dPos = ext.dpos(td_dl)
-        return (bu_dt, dLevels, dPos, bu_w1, bu_db1, bu_w2, bu_b2,
-                td_w1, td_db1, td_w2, td_b2, None, None, None, None, None,
-                None, None, None, None, None)
+        return _step_grads(bu_dt, dLevels, dPos, bu_w1, bu_db1, bu_w2, bu_b2,
+                           td_w1, td_db1, td_w2, td_b2)
+
+
+# GlomStepFn's saved tensors, in save_for_backward order
+_Saved = collections.namedtuple(
+    "_Saved", "tokens levels pos bw1 bw2 tw1 tw2 bhp bha thp tha probs rnorm "
+              "mask bw1t bw2t tw1t tw2t tdin")
+
+
+def _step_grads(*grads):
+    """Eleven real gradients, then None for GlomStepFn's ten other inputs."""
+    return grads + (None,) * 10
+
+
+def _bwd_path(merge=False):
+    """'single' (GLOM_NO_BWD_STREAMS=1, which wins), 'fork4' (GLOM_BWD_FORK
+    set to anything but 3), else 'fork3', or 'merged' where asked for."""
+    if os.environ.get("GLOM_NO_BWD_STREAMS", "0") == "1":
+        return "single"
+    if os.environ.get("GLOM_BWD_FORK", "3") != "3":
+        return "fork4"
+    return "merged" if merge else "fork3"
+
+
+def _bwd_begin(ctx, dnew):
+    """(ext, saved tensors, first live level), after the check mode's test."""
+    lo = ctx.cone[0] if ctx.cone is not None else 0
+    if lo > 0 and CHECK_LEVEL_CONE:
+        _check_cone(dnew, lo, ctx.cone[1])
+    return _load_extension(), _Saved(*ctx.saved_tensors), lo
 
 
 def _transposed_weights(model):
@@ -692,17 +693,21 @@ def _needs_bwd(*tensors):
         t is not None and t.requires_grad for t in tensors)
 
 
-def glom_step(model, tokens, levels, pos, mask, wts=None, slab_ref=None,
-              cone=None, carry=None):
+def _step_args(model, tokens, levels, pos):
+    """The first eleven arguments of GlomStepFn and ext.glom_step_fwd."""
     bw = model.bottom_up.net
     tw = model.top_down.net
-    if wts is None:
-        wts = (None, None, None, None)
-    args = (tokens, levels, pos,
+    return (tokens, levels, pos,
             bw[1].weight[..., 0], bw[1].bias, bw[3].weight[..., 0],
             bw[3].bias,
             tw[1].weight[..., 0], tw[1].bias, tw[3].weight[..., 0],
             tw[3].bias)
+
+
+def glom_step(model, tokens, levels, pos, mask, wts=None, slab_ref=None,
+              cone=None, carry=None):
+    wts = wts or (None,) * 4
+    args = _step_args(model, tokens, levels, pos)
     if carry is not None:
         # group 0 may be skipped when nothing will read this step's group-0
         # Hpre / Hact: no backward is recorded, or its cone starts above 0
@@ -804,8 +809,7 @@ def glom_forward(model, img, iters, levels=None, return_all=False,
     # and the default 3-way backward fork
     merge = (loss_level_min is not None and BWD_MERGE
              and os.environ.get("GLOM_NO_BWD_MERGE", "0") != "1"
-             and os.environ.get("GLOM_NO_BWD_STREAMS", "0") != "1"
-             and os.environ.get("GLOM_BWD_FORK", "3") == "3"
+             and _bwd_path(merge=True) == "merged"
              and model.dim % 8 == 0 and model.levels >= 2
              and 0 < grad_iters <= iters and torch.is_grad_enabled())
     if merge:
@@ -833,8 +837,6 @@ def glom_forward(model, img, iters, levels=None, return_all=False,
                 steps.append(levels)
         if overlap:
             ext = _load_extension()
-            bw = model.bottom_up.net
-            tw = model.top_down.net
             s_tail = _tail_stream()
             ev = torch.cuda.Event()
             ev.record(torch.cuda.current_stream())
@@ -849,11 +851,7 @@ def glom_forward(model, img, iters, levels=None, return_all=False,
                 for t in range(n_sync, iters):
                     emit = carry.fuse and t < iters - 1
                     outs = ext.glom_step_fwd(
-                        tokens, levels, pos,
-                        bw[1].weight[..., 0], bw[1].bias,
-                        bw[3].weight[..., 0], bw[3].bias,
-                        tw[1].weight[..., 0], tw[1].bias,
-                        tw[3].weight[..., 0], tw[3].bias,
+                        *_step_args(model, tokens, levels, pos),
                         model.attention.attend_self, mask, slab, t + 1,
                         FORCE_SAVE_FOR_BWD, carry.bu0, carry.td_in,
                         carry.rnorm, emit)

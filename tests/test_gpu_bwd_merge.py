@@ -299,6 +299,32 @@ def test_no_fill_ops_feed_merge_and_dpos(shape):
     assert z.shape == (N, d) and not _bits(z).any()
 
 
+def test_merged_top_down_call_equals_the_compact_filled_call():
+    """The top-down call exactly as the merged backward makes it, dmix read
+    in place at row stride L*d, dB2 handed in from db2_cone and no_fill
+    set, against the compact-dY call that fills: dLevels over the levels
+    [g_lo + 1, L) that the no-fill contract says are written, every weight
+    and bias gradient everywhere, for every first live group."""
+    ext = _ext()
+    B, N, L, d = 2, 256, 4, 256
+    td = _ff_case(B, N, L, d, 1)
+    for g_lo in range(td["G"] + 1):
+        dmix = _dmix_lo(B, N, L, d, g_lo)
+        ref = _ff_bwd(td, 1, dmix[:, :, :L - 1].contiguous(), g_lo)
+        b2_td = ext.db2_cone(dmix, g_lo)[1]
+        _poison_free_blocks(dmix, 4)
+        got = _ff_bwd(td, 1, dmix, g_lo, L * d, b2_td, True)
+        torch.cuda.synchronize()
+        lo, hi = _ranges(g_lo, L)[0][2]       # the top-down range
+        assert (lo, hi) == (g_lo + 1, L)
+        assert torch.equal(got[1][:, :, lo:hi], ref[1][:, :, lo:hi]), g_lo
+        assert _same(got[1][:, :, lo:hi], ref[1][:, :, lo:hi]), g_lo
+        for i in (0, 2, 3, 4, 5):
+            assert torch.equal(got[i], ref[i]) and _same(got[i], ref[i]), \
+                (g_lo, OUT6[i])
+        assert got[5].data_ptr() == b2_td.data_ptr()
+
+
 # ------------------------------ 3. model ------------------------------- #
 
 # image_size == patch_size is the smallest image a model accepts (one

@@ -1,5 +1,5 @@
 """Dispatch-coverage sweep: drive every GEMM kernel variant (v1 predicated,
-nt_fast 128^2, nt_fast3/4 128x256, tn_fast(+split-K), nn_fast) through the
+nt_fast 128^2, nt_fast4 128x256, tn_fast(+split-K), nn_fast) through the
 grouped-FF and consensus ops across shapes, checking against fp32 torch on
 the same bf16 inputs."""
 
