@@ -11,7 +11,7 @@ checkpoints interchange with the plain-optimizer path.
 hipGraph-replay-safe: the step counter lives in a device tensor that the
 norm-finalize kernel increments, so a captured step() stays correct across
 replays; ``steps_done()`` syncs the host mirror (one device read) before
-checkpointing.
+checkpointing. The device counter is fp32 and exact up to 2^24 steps.
 
 Per-param step caveat: torch increments a param's ``step`` only on steps
 where it received a gradient; this class uses the global step count for

@@ -84,7 +84,15 @@ def test_sched_groups_match_torch(clip):
 
     fused = FusedAdamW(params, masters, lr=lr, weight_decay=wd,
                        lr_scale=scale, max_grad_norm=clip, schedule=sc)
-    _run(fused, params, grads_seq)
+    # each step also per element against fp64, from the state before it and
+    # the learning rate the device evaluated for it
+    from _stream_util import check_fused_step, opt_snapshot
+    for t, grads in enumerate(grads_seq, 1):
+        before = opt_snapshot(fused)
+        _run(fused, params, [grads])
+        lr_t = fused.current_lr()
+        check_fused_step(fused, before, grads, t, [lr_t * s for s in scale],
+                         wd)
 
     groups = [{"params": [ref[0]], "weight_decay": 1e-2, "scale": 0.5},
               {"params": [ref[1], ref[2]], "weight_decay": 0.0, "scale": 1.0},

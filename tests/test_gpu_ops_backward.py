@@ -104,6 +104,17 @@ def test_level_mix_backward():
         r = _rel(a, b)
         assert r < 2e-2, (name, r)
 
+    # per element against fp64: the forward within the bound mix_ref
+    # derives, the gradients bit for bit (one divide by 3 or 4 rounds once)
+    from _bounds_util import assert_exact, assert_within
+    from _stream_util import mix_bwd_ref, mix_ref
+    ref64, tol = mix_ref(lv.detach(), bu.detach(), td.detach(), cons.detach())
+    assert_within(out.detach(), ref64, tol, "out")
+    dmix64, dtd64 = mix_bwd_ref(gout)
+    for name, a in zip(["lv", "bu", "cons"], (g[0], g[1], g[3])):
+        assert_exact(a, dmix64, name)
+    assert_exact(g[2], dtd64, "td")
+
 
 def test_full_graph_token_grad_nonzero():
     """The patch-token gradient path through every iteration must be live."""

@@ -137,10 +137,15 @@ def test_fused_adamw_matches_torch(clip):
 
     fused = FusedAdamW(params, masters, lr=1e-2,
                        max_grad_norm=clip)
-    for grads in grads_seq:
+    # each step also per element against fp64, from the state before it
+    from _stream_util import check_fused_step, opt_snapshot
+    n = len(shapes)
+    for t, grads in enumerate(grads_seq, 1):
+        before = opt_snapshot(fused)
         for p, g in zip(params, grads):
             p.grad = g
         fused.step()
+        check_fused_step(fused, before, grads, t, [1e-2] * n, [1e-2] * n)
 
     ref, _ = _torch_adamw_reference(ref_masters, grads_seq, 1e-2, clip)
     for m, r in zip(masters, ref):
