@@ -1455,6 +1455,27 @@ torch::Tensor gemm_nn(torch::Tensor A, torch::Tensor B) {
     return C;
 }
 
+// Test-only: the raw f32 partials (sk, G, M, N) of gemm_nn_sk for A (G,M,K),
+// B (G,K,N); the caller sums the slices. The kernel's one production user
+// (the contrastive backward) feeds it non-integer operands.
+torch::Tensor gemm_nn_splitk(torch::Tensor A, torch::Tensor B, int64_t sk) {
+    CHECK_IN(A); CHECK_IN(B);
+    TORCH_CHECK(A.dim() == 3 && B.dim() == 3 && A.size(0) == B.size(0)
+                && A.size(2) == B.size(1), "A (G,M,K), B (G,K,N)");
+    const int64_t G = A.size(0), M = A.size(1), K = A.size(2),
+                  N = B.size(2);
+    TORCH_CHECK(M % 128 == 0 && N % 128 == 0 && K % 8 == 0 && sk >= 1
+                && sk <= 16, "gemm_nn_sk needs full 128^2 tiles, K / 8");
+    auto ws = torch::empty({sk, G, M, N}, A.options().dtype(at::kFloat));
+    GemmParams p = base_params(M, N, K, LAYOUT_NN, G, G, 1.0f);
+    p.A.base = A.data_ptr(); p.A.sin = M * K; p.A.ld = K;
+    p.B.base = B.data_ptr(); p.B.sin = K * N; p.B.ld = N;
+    p.splitk = (int)sk; p.ws = ws.data_ptr<float>();
+    launch_gemm_nn_sk(p, cur_stream());
+    check_launch();
+    return ws;
+}
+
 void add4_into(torch::Tensor a, torch::Tensor b, torch::Tensor c,
                torch::Tensor d, torch::Tensor out) {
     CHECK_IN(a); CHECK_IN(b); CHECK_IN(c); CHECK_IN(d); CHECK_IN(out);
@@ -2198,6 +2219,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("gemm_nt", &gemm_nt, "C = A B^T + bias per group (tests only)",
           py::arg("A"), py::arg("B"), py::arg("bias") = c10::nullopt);
     m.def("gemm_nn", &gemm_nn, "C = A B per group (tests only)");
+    m.def("gemm_nn_splitk", &gemm_nn_splitk,
+          "f32 split-K partials of A B per group (tests only)");
     m.def("set_wide_epilogue", &set_wide_epilogue,
           "toggle the 16-byte register epilogue of nt5p (A/B)");
     m.def("set_wide_epilogue_mode", &set_wide_epilogue_mode,

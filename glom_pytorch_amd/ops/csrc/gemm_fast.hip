@@ -54,7 +54,7 @@ __device__ __forceinline__ float kq_sum(float v) {
 // Issue this wave's share of one operand tile (128 rows x 64 cols bf16 =
 // 16 KB = 16 DMA chunks of 1 KB; 4 chunks per wave) into a LINEAR LDS
 // image, pre-swizzling the source address so a swizzled ds_read_b128 is
-// conflict-free (byte_in_row ^= (row&7)<<4).
+// conflict-free (granule ^= swz_row(row), lds_swizzle.h).
 __device__ __forceinline__ void stage_glds(
         ushort_t* lds, const ushort_t* src, long ld, int r0, int k0,
         int wid, int lane) {
@@ -62,7 +62,7 @@ __device__ __forceinline__ void stage_glds(
     for (int c = 0; c < 4; c++) {
         int chunk = wid * 4 + c;
         int row = chunk * 8 + (lane >> 3);
-        int swz8 = ((lane & 7) ^ swz_row(row)) * 8;
+        int swz8 = ((lane & 7) ^ swz_row<SWZ_NT_FAST>(row)) * 8;
         const ushort_t* gaddr = src + (long)(r0 + row) * ld + k0 + swz8;
         ushort_t* laddr = lds + chunk * 512;  // wave-uniform chunk base
         __builtin_amdgcn_global_load_lds(
@@ -131,13 +131,13 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nt_fast_kernel(GemmParams p) {
 #pragma unroll
             for (int i = 0; i < 4; i++) {
                 int row = wm + i * 16 + lrow;
-                int off = (s * 32 + kq * 8) ^ (swz_row(row) << 3);
+                int off = (s * 32 + kq * 8) ^ (swz_row<SWZ_NT_FAST>(row) << 3);
                 af[s][i] = *(const short8*)&As0[cur * BM * FBK + row * FBK + off];
             }
 #pragma unroll
             for (int j = 0; j < 4; j++) {
                 int row = wn + j * 16 + lrow;
-                int off = (s * 32 + kq * 8) ^ (swz_row(row) << 3);
+                int off = (s * 32 + kq * 8) ^ (swz_row<SWZ_NT_FAST>(row) << 3);
                 bfr[s][j] = *(const short8*)&Bs0[cur * BN * FBK + row * FBK + off];
             }
         }
@@ -204,9 +204,10 @@ __global__ __launch_bounds__(NTHREADS) void gemm_tn_fast_kernel(GemmParams p) {
 
     for (int k0 = k_begin; k0 < k_end; k0 += FBK) {
         if (threadIdx.x < 128)
-            stage_repack(As, Ap, lda, k0, m0, k_end, threadIdx.x);
+            stage_repack<SWZ_TN_FAST>(As, Ap, lda, k0, m0, k_end, threadIdx.x);
         else
-            stage_repack(Bs, Bp, ldb, k0, n0, k_end, threadIdx.x - 128);
+            stage_repack<SWZ_TN_FAST>(Bs, Bp, ldb, k0, n0, k_end,
+                                      threadIdx.x - 128);
         __syncthreads();
         short8 af[2][4], bfr[2][4];
 #pragma unroll
@@ -214,13 +215,13 @@ __global__ __launch_bounds__(NTHREADS) void gemm_tn_fast_kernel(GemmParams p) {
 #pragma unroll
             for (int i = 0; i < 4; i++) {
                 int row = wm + i * 16 + lrow;
-                int off = (s * 32 + kq * 8) ^ (swz_row(row) << 3);
+                int off = (s * 32 + kq * 8) ^ (swz_row<SWZ_TN_FAST>(row) << 3);
                 af[s][i] = *(const short8*)&As[row * FBK + off];
             }
 #pragma unroll
             for (int j = 0; j < 4; j++) {
                 int row = wn + j * 16 + lrow;
-                int off = (s * 32 + kq * 8) ^ (swz_row(row) << 3);
+                int off = (s * 32 + kq * 8) ^ (swz_row<SWZ_TN_FAST>(row) << 3);
                 bfr[s][j] = *(const short8*)&Bs[row * FBK + off];
             }
         }
@@ -308,9 +309,10 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nn_fast_kernel(GemmParams p) {
 
     for (int k0 = 0; k0 < p.K; k0 += FBK) {
         if (threadIdx.x < 128)
-            stage_copy128(As, Ap, lda, m0, k0, p.K, threadIdx.x);
+            stage_copy128<SWZ_NN_FAST>(As, Ap, lda, m0, k0, p.K, threadIdx.x);
         else
-            stage_repack(Bs, Bp, ldb, k0, n0, p.K, threadIdx.x - 128);
+            stage_repack<SWZ_NN_FAST>(Bs, Bp, ldb, k0, n0, p.K,
+                                      threadIdx.x - 128);
         __syncthreads();
         short8 af[2][4], bfr[2][4];
 #pragma unroll
@@ -318,13 +320,13 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nn_fast_kernel(GemmParams p) {
 #pragma unroll
             for (int i = 0; i < 4; i++) {
                 int row = wm + i * 16 + lrow;
-                int off = (s * 32 + kq * 8) ^ (swz_row(row) << 3);
+                int off = (s * 32 + kq * 8) ^ (swz_row<SWZ_NN_FAST>(row) << 3);
                 af[s][i] = *(const short8*)&As[row * FBK + off];
             }
 #pragma unroll
             for (int j = 0; j < 4; j++) {
                 int row = wn + j * 16 + lrow;
-                int off = (s * 32 + kq * 8) ^ (swz_row(row) << 3);
+                int off = (s * 32 + kq * 8) ^ (swz_row<SWZ_NN_FAST>(row) << 3);
                 bfr[s][j] = *(const short8*)&Bs[row * FBK + off];
             }
         }
@@ -359,7 +361,20 @@ void launch_gemm_nn_fast(const GemmParams& p, hipStream_t stream) {
 
 #define NT3 512
 #define BN3 256
-#define EPI2_ROW 264   // 256 cols + 8 pad (16B-aligned LDS epilogue rows)
+// 256 cols + 16 pad (16B-aligned LDS epilogue rows). The fused AV product
+// reads its P operand from these rows as MFMA fragments: with 34 granules
+// per row, row r at kq sits on 16-byte slot (2r + kq) mod 16, and a read
+// group (8 rows at kq, the other 8 at kq+1, never r and r+8 together) gets
+// 16 distinct slots. The former pad of 8 (slot r + kq) was 2-way in every
+// group. The price: the 2-byte fragment-order stores into these rows count
+// more conflict cycles with 34 granules per row than with 33 (+3.1M per
+// plain call at 16256x1024x512 G6, +0.8M on the fused forward against
+// -1.57M for its P reads; profiles/README.md). No pad clears both.
+#define EPI2_ROW 272
+static_assert(lds_model::p_read_worst(EPI2_ROW) == 4,
+              "P-operand fragment reads of the fused AV must not conflict");
+static_assert(128 * EPI2_ROW + 2 * 256 * FBK <= 3 * (128 + 256) * FBK,
+              "epilogue rows + the two V buffers must fit the nt4 arena");
 
 // ------- 3-ring stages, counted vmcnt, raw barriers, LDS epilogue ------
 __global__ __launch_bounds__(NT3) void gemm_nt_fast4_kernel(GemmParams p) {
@@ -399,7 +414,7 @@ __global__ __launch_bounds__(NT3) void gemm_nt_fast4_kernel(GemmParams p) {
         for (int c = 0; c < 2; c++) {
             int chunk = wid * 2 + c;
             int row = chunk * 8 + (lane >> 3);
-            int swz8 = ((lane & 7) ^ swz_row(row)) * 8;
+            int swz8 = ((lane & 7) ^ swz_row<SWZ_NT4>(row)) * 8;
             const ushort_t* g = Ap + (long)(m0 + row) * lda + k0 + swz8;
             __builtin_amdgcn_global_load_lds(
                 (const __attribute__((address_space(1))) unsigned int*)g,
@@ -410,7 +425,7 @@ __global__ __launch_bounds__(NT3) void gemm_nt_fast4_kernel(GemmParams p) {
         for (int c = 0; c < 4; c++) {
             int chunk = wid * 4 + c;
             int row = chunk * 8 + (lane >> 3);
-            int swz8 = ((lane & 7) ^ swz_row(row)) * 8;
+            int swz8 = ((lane & 7) ^ swz_row<SWZ_NT4>(row)) * 8;
             const ushort_t* g = Bp + (long)(n0 + row) * ldb + k0 + swz8;
             __builtin_amdgcn_global_load_lds(
                 (const __attribute__((address_space(1))) unsigned int*)g,
@@ -441,13 +456,13 @@ __global__ __launch_bounds__(NT3) void gemm_nt_fast4_kernel(GemmParams p) {
 #pragma unroll
             for (int i = 0; i < 4; i++) {
                 int row = wm + i * 16 + lrow;
-                int off = (s * 32 + kq * 8) ^ (swz_row(row) << 3);
+                int off = (s * 32 + kq * 8) ^ (swz_row<SWZ_NT4>(row) << 3);
                 af[s][i] = *(const short8*)&Al[row * FBK + off];
             }
 #pragma unroll
             for (int j = 0; j < 4; j++) {
                 int row = wn + j * 16 + lrow;
-                int off = (s * 32 + kq * 8) ^ (swz_row(row) << 3);
+                int off = (s * 32 + kq * 8) ^ (swz_row<SWZ_NT4>(row) << 3);
                 bfr[s][j] = *(const short8*)&Bl[row * FBK + off];
             }
         }
@@ -661,7 +676,7 @@ __global__ __launch_bounds__(NT3) void gemm_nt_fast4_kernel(GemmParams p) {
                             for (int r = 0; r < 8; r++)
                                 col.u[r] = rv[r].u[e];
                             int row = cb * 8 + e;
-                            int off = (mb * 8) ^ (swz_row(row) << 3);
+                            int off = (mb * 8) ^ (swz_row<SWZ_NT4_V>(row) << 3);
                             *(uint4v*)&Vt[row * FBK + off] = col.v;
                         }
                     }
@@ -688,7 +703,7 @@ __global__ __launch_bounds__(NT3) void gemm_nt_fast4_kernel(GemmParams p) {
                         for (int j = 0; j < 4; j++) {
                             int row = wcol64 + j * 16 + lrow;
                             int off = (ss * 32 + kq * 8)
-                                      ^ (swz_row(row) << 3);
+                                      ^ (swz_row<SWZ_NT4_V>(row) << 3);
                             vbf[ss][j] = *(const short8*)&Vt[
                                 row * FBK + off];
                         }
@@ -1047,7 +1062,7 @@ __global__ __launch_bounds__(NT3) void gemm_nt_fast5p_kernel(GemmParams p) {
         for (int c = 0; c < 2; c++) {
             int chunk = wid * 2 + c;
             int row = chunk * 8 + (lane >> 3);
-            int swz8 = ((lane & 7) ^ swz_row(row)) * 8;
+            int swz8 = ((lane & 7) ^ swz_row<SWZ_NT5P>(row)) * 8;
             const ushort_t* g_ = Ap + (long)(mt0 + row) * lda + k0 + swz8;
             __builtin_amdgcn_global_load_lds(
                 (const __attribute__((address_space(1))) unsigned int*)g_,
@@ -1058,7 +1073,7 @@ __global__ __launch_bounds__(NT3) void gemm_nt_fast5p_kernel(GemmParams p) {
         for (int c = 0; c < 4; c++) {
             int chunk = wid * 4 + c;
             int row = chunk * 8 + (lane >> 3);
-            int swz8 = ((lane & 7) ^ swz_row(row)) * 8;
+            int swz8 = ((lane & 7) ^ swz_row<SWZ_NT5P>(row)) * 8;
             const ushort_t* g_ = Bp + (long)(n0 + row) * ldb + k0 + swz8;
             __builtin_amdgcn_global_load_lds(
                 (const __attribute__((address_space(1))) unsigned int*)g_,
@@ -1108,13 +1123,13 @@ __global__ __launch_bounds__(NT3) void gemm_nt_fast5p_kernel(GemmParams p) {
 #pragma unroll
             for (int i = 0; i < 4; i++) {
                 int row = wm + i * 16 + lrow;
-                int off = (s * 32 + kq * 8) ^ (swz_row(row) << 3);
+                int off = (s * 32 + kq * 8) ^ (swz_row<SWZ_NT5P>(row) << 3);
                 af[s][i] = *(const short8*)&Al[row * FBK + off];
             }
 #pragma unroll
             for (int j = 0; j < 4; j++) {
                 int row = wn + j * 16 + lrow;
-                int off = (s * 32 + kq * 8) ^ (swz_row(row) << 3);
+                int off = (s * 32 + kq * 8) ^ (swz_row<SWZ_NT5P>(row) << 3);
                 bfr[s][j] = *(const short8*)&Bl[row * FBK + off];
             }
         }
@@ -1451,7 +1466,7 @@ __global__ __launch_bounds__(NT8) void gemm_nt_fast8p_kernel(GemmParams p) {
 #pragma unroll
         for (int c = 0; c < 2; c++) {
             int row = row0 + c * 8 + (lane >> 3);
-            int swz8 = ((lane & 7) ^ swz_row(row)) * 8;
+            int swz8 = ((lane & 7) ^ swz_row<SWZ_NT8P>(row)) * 8;
             const ushort_t* g = src + (long)(g0 + row) * ld + k0 + swz8;
             __builtin_amdgcn_global_load_lds(
                 (const __attribute__((address_space(1))) unsigned int*)g,
@@ -1478,7 +1493,7 @@ __global__ __launch_bounds__(NT8) void gemm_nt_fast8p_kernel(GemmParams p) {
 #pragma unroll
             for (int j = 0; j < 4; j++) {
                 int row = wn + j * 16 + lrow;
-                int off = (s * 32 + kq * 8) ^ (swz_row(row) << 3);
+                int off = (s * 32 + kq * 8) ^ (swz_row<SWZ_NT8P>(row) << 3);
                 bfrag[s][j] = *(const short8*)&Bl[row * FBK + off];
             }
 #pragma unroll
@@ -1489,7 +1504,7 @@ __global__ __launch_bounds__(NT8) void gemm_nt_fast8p_kernel(GemmParams p) {
 #pragma unroll
                 for (int i = 0; i < 2; i++) {
                     int row = wm + (2 * ph + i) * 16 + lrow;
-                    int off = (s * 32 + kq * 8) ^ (swz_row(row) << 3);
+                    int off = (s * 32 + kq * 8) ^ (swz_row<SWZ_NT8P>(row) << 3);
                     af[s][i] = *(const short8*)&Al[row * FBK + off];
                 }
             if (more) stage2((t + 1) & 1, (t + 1) * FBK, ph);
@@ -1670,9 +1685,10 @@ __global__ __launch_bounds__(NTHREADS) void gemm_tn_sk_kernel(GemmParams p) {
 
     for (int k0 = k_begin; k0 < k_end; k0 += FBK) {
         if (threadIdx.x < 128)
-            stage_repack(As, Ap, lda, k0, m0, k_end, threadIdx.x);
+            stage_repack<SWZ_TN_SK>(As, Ap, lda, k0, m0, k_end, threadIdx.x);
         else
-            stage_repack(Bs, Bp, ldb, k0, n0, k_end, threadIdx.x - 128);
+            stage_repack<SWZ_TN_SK>(Bs, Bp, ldb, k0, n0, k_end,
+                                    threadIdx.x - 128);
         __syncthreads();
         short8 af[2][4], bfr[2][4];
 #pragma unroll
@@ -1680,13 +1696,13 @@ __global__ __launch_bounds__(NTHREADS) void gemm_tn_sk_kernel(GemmParams p) {
 #pragma unroll
             for (int i = 0; i < 4; i++) {
                 int row = wm + i * 16 + lrow;
-                int off = (s * 32 + kq * 8) ^ (swz_row(row) << 3);
+                int off = (s * 32 + kq * 8) ^ (swz_row<SWZ_TN_SK>(row) << 3);
                 af[s][i] = *(const short8*)&As[row * FBK + off];
             }
 #pragma unroll
             for (int j = 0; j < 4; j++) {
                 int row = wn + j * 16 + lrow;
-                int off = (s * 32 + kq * 8) ^ (swz_row(row) << 3);
+                int off = (s * 32 + kq * 8) ^ (swz_row<SWZ_TN_SK>(row) << 3);
                 bfr[s][j] = *(const short8*)&Bs[row * FBK + off];
             }
         }

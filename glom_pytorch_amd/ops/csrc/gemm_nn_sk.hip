@@ -53,9 +53,10 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nn_sk_kernel(GemmParams p) {
 
     for (int k0 = k_begin; k0 < k_end; k0 += FBK) {
         if (threadIdx.x < 128)
-            stage_copy128(As, Ap, lda, m0, k0, k_end, threadIdx.x);
+            stage_copy128<SWZ_NN_SK>(As, Ap, lda, m0, k0, k_end, threadIdx.x);
         else
-            stage_repack(Bs, Bp, ldb, k0, n0, k_end, threadIdx.x - 128);
+            stage_repack<SWZ_NN_SK>(Bs, Bp, ldb, k0, n0, k_end,
+                                    threadIdx.x - 128);
         __syncthreads();
         short8 af[2][4], bfr[2][4];
 #pragma unroll
@@ -63,13 +64,13 @@ __global__ __launch_bounds__(NTHREADS) void gemm_nn_sk_kernel(GemmParams p) {
 #pragma unroll
             for (int i = 0; i < 4; i++) {
                 int row = wm + i * 16 + lrow;
-                int off = (s * 32 + kq * 8) ^ (swz_row(row) << 3);
+                int off = (s * 32 + kq * 8) ^ (swz_row<SWZ_NN_SK>(row) << 3);
                 af[s][i] = *(const short8*)&As[row * FBK + off];
             }
 #pragma unroll
             for (int j = 0; j < 4; j++) {
                 int row = wn + j * 16 + lrow;
-                int off = (s * 32 + kq * 8) ^ (swz_row(row) << 3);
+                int off = (s * 32 + kq * 8) ^ (swz_row<SWZ_NN_SK>(row) << 3);
                 bfr[s][j] = *(const short8*)&Bs[row * FBK + off];
             }
         }
